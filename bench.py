@@ -27,6 +27,7 @@ The line also carries
                 `value` stays the single-stream number
   host_image_path / pinned_h2d_path   the PCIe-inclusive entry points (never `value`)
 `--config hd2mm | bigmap` run the 1280x720 / 2 mm workload (on a 416 MB map for bigmap) as the main line.
+`--dump-outputs DIR` writes the map the timed steps built as .npy files (dump_outputs()), to compare two builds.
 """
 import argparse
 import json
@@ -44,18 +45,30 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 
 
-def parse():
+# Defaults of the options whose value depends on --config (config_defaults()): an option given on the command line is
+# always taken as given.
+CONFIG_DEFAULTS = {
+    "vga5mm": dict(steps=60, warmup=3, reps=5, frames_per_step=90, cpu_frames=1080, flythrough_frames=180),
+    "hd2mm": dict(steps=60, warmup=3, reps=5, frames_per_step=30, cpu_frames=60, flythrough_frames=180),
+    # 120 frames of a 1 degree/frame sweep, there and back; parity on the first frames only (the CPU runs ~30 frames/s)
+    "bigmap": dict(steps=2, warmup=1, reps=3, frames_per_step=240, cpu_frames=8, flythrough_frames=180),
+    "flythrough": dict(steps=60, warmup=3, reps=5, frames_per_step=90, cpu_frames=1080, flythrough_frames=360),
+}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=60)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--frames-per-step", type=int, default=90)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps per repetition (default 60; bigmap: 2)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 3; bigmap: 1)")
+    ap.add_argument("--frames-per-step", type=int, default=None,
+                    help="frames per step (default 90; hd2mm: 30; bigmap: 240)")
     ap.add_argument("--cam", default="scannet")
     ap.add_argument("--scene", default="room")
     ap.add_argument("--voxel", type=float, default=0.005)
     ap.add_argument("--max-depth", type=float, default=4.0)
-    ap.add_argument("--cpu-frames", type=int, default=1080,
-                    help="frames of the stream timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=None,
+                    help="frames of the stream timed on the CPU oracle (0 = skip; default 1080; hd2mm: 60; bigmap: 8)")
     ap.add_argument("--config", default="vga5mm", choices=["vga5mm", "hd2mm", "bigmap", "flythrough"],
                     help="vga5mm: BASELINE metric config (640x480, 5 mm); hd2mm: 1280x720, 2 mm "
                          "(BASELINE configs[3] workload, single GPU unless --shard); bigmap: hd2mm on a "
@@ -78,17 +91,34 @@ def parse():
                     help="frames timed through the host-image entry point, PCIe included (0 = skip)")
     ap.add_argument("--sync-every", type=int, default=0,
                     help="diagnostic: host-synchronise every N frames (0 = only at the end)")
-    ap.add_argument("--reps", type=int, default=5,
-                    help="timed repetitions of the K steps; value = the median repetition")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of the K steps; value = the median repetition (default 5; bigmap: 3)")
     ap.add_argument("--streams", type=int, default=4,
                     help="N = 1: also time S concurrent streams on this GPU through one launch "
                          "triple per frame step (ratsdf_group_*); 0 / 1 = skip")
     ap.add_argument("--no-secondary", action="store_true",
                     help="vga5mm, N = 1: skip the bounded 1280x720 / 2 mm legs (`secondary`: hd2mm, bigmap), the "
                          "non-repeating pass (`flythrough`) and the C++ TSDFSystem leg (`tsdf_system_path`)")
-    ap.add_argument("--flythrough-frames", type=int, default=180,
-                    help="frames of the non-repeating pass (`flythrough`; --config flythrough: 360 at 1280x720)")
-    return ap.parse_args()
+    ap.add_argument("--flythrough-frames", type=int, default=None,
+                    help="frames of the non-repeating pass (`flythrough`, default 180; --config flythrough: 360 at 1280x720)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the last timed step, write the map as DIR/<name>.npy, float32 / float64, at most 64 MB "
+                         "(dump_outputs()): the map of all warm-up and timed steps (warmup + reps x steps), rank 0's "
+                         "(with --shard: rank 0's subvolume); the inputs depend on the arguments only")
+    return config_defaults(ap.parse_args(argv))
+
+
+def config_defaults(a):
+    """Fills in what --config implies: its workload, and the defaults of the options not given on the command line."""
+    for k, v in CONFIG_DEFAULTS[a.config].items():
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+    if a.config in ("hd2mm", "bigmap"):
+        a.cam, a.voxel = "l515_720p", 0.002
+    if a.config == "bigmap":
+        a.host_frames = 0
+        a.streams = 0
+    return a
 
 
 def make_stream(scene, cam, nframes, phase):
@@ -102,6 +132,41 @@ def make_stream(scene, cam, nframes, phase):
 def alg_bytes(W, H, tot):
     """15 W H + 12 V + 24 U per frame, summed over the frames counted in `tot`."""
     return 15.0 * W * H * tot["frames"] + 12.0 * tot["visible_blocks"] + 24.0 * tot["updated_voxels"]
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all arrays together
+DUMP_MAX_BLOCKS = 4096        # voxel blocks written whole (12 KiB each as float32); a larger map is sampled
+DUMP_SEED = 20240607
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the map the warm-up and timed steps left behind (warmup + reps x steps steps), as a caller reads
+    it back (directory + voxels), written as float32 / float64 .npy files.  Blocks are ordered by their coordinates,
+    so two builds that build the same map write the same arrays whatever pool slots they chose; a map of more than
+    DUMP_MAX_BLOCKS blocks is represented by a fixed, seeded sample of them (the whole directory is always written).
+        blocks.npy        [n, 3] float64  block coordinates of every active block (x, y, z), sorted
+        sample_index.npy  [k]    float64  rows of blocks.npy whose voxels follow
+        tsdf.npy / prob.npy / weight.npy  [k, 512] float32;  rgb.npy  [k, 512, 3] float32"""
+    from ratsdf._abi import BLOCK_VOLUME
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    _, blocks = eng.dump_directory()
+    blocks = blocks[np.lexsort((blocks["z"], blocks["y"], blocks["x"]))]
+    xyz = np.stack([blocks["x"], blocks["y"], blocks["z"]], axis=1).astype(np.float64)
+    per_block = BLOCK_VOLUME * 4 * (1 + 1 + 1 + 3)
+    k = int(min(len(blocks), DUMP_MAX_BLOCKS, (DUMP_LIMIT_BYTES - xyz.nbytes - (1 << 20)) // per_block))
+    if k < len(blocks):
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(len(blocks), size=k, replace=False))
+    else:
+        sel = np.arange(len(blocks))
+    tsdf, rgbw, prob = eng.dump_voxels(blocks["idx"][sel])
+    arrays = {"blocks": xyz, "sample_index": sel.astype(np.float64), "tsdf": tsdf, "prob": prob,
+              "weight": rgbw["weight"].astype(np.float32),
+              "rgb": np.stack([rgbw["r"], rgbw["g"], rgbw["b"]], axis=-1).astype(np.float32)}
+    for name, arr in arrays.items():
+        np.save(out_dir / f"{name}.npy", arr)
+    return {"dir": str(out_dir), "active_blocks": len(blocks), "blocks_with_voxels": k,
+            "bytes": int(sum(arr.nbytes for arr in arrays.values()))}
 
 
 def traffic_file(config):
@@ -580,6 +645,7 @@ def bench_sharded_stream(a, rank, world, dev, dev_index, backend, torch, dist, r
         eng.profile_enable(False)
     tot = eng.totals()
     stats = eng.last_frame_stats()
+    dumped = dump_outputs(eng, a.dump_outputs) if (a.dump_outputs and rank == 0) else None   # rank 0's subvolume
     shares = [None] * world
     dist.all_gather_object(shares, dict(visible_blocks=round(tot["visible_blocks"] / max(tot["frames"], 1), 1),
                                         updated_voxels=round(tot["updated_voxels"] / max(tot["frames"], 1), 1),
@@ -625,6 +691,8 @@ def bench_sharded_stream(a, rank, world, dev, dev_index, backend, torch, dist, r
                       "active_blocks": stats["active_blocks"], "note": "rank 0's subvolume"},
             "roofline": roof, "cpu_baseline": None, "parity": parity,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
     eng.close()
     return out
 
@@ -706,16 +774,12 @@ def main():
             dist.init_process_group(backend)
 
     import ratsdf
-    if a.config == "hd2mm":
-        a.cam, a.voxel = "l515_720p", 0.002
-        if a.frames_per_step == 90:
-            a.frames_per_step = 30
-        if a.cpu_frames == 1080:
-            a.cpu_frames = 60
     if a.config == "flythrough":   # the non-repeating pass as the whole run (1280x720 / 2 mm, a full circle)
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: --config flythrough has no timed steps; use another --config")
         if not torch.cuda.is_available():
             raise SystemExit("needs a GPU")
-        n = a.flythrough_frames if a.flythrough_frames != 180 else 360
+        n = a.flythrough_frames
         out = bench_flythrough(ratsdf, torch, dev, dev_index, "l515_720p", 0.002, a.max_depth, n,
                                min(len(os.sched_getaffinity(0)), 16), n_par=n)  # parity over the WHOLE pass
         out = {"metric": "depth+semantic frames/sec integrated @1280x720, 2mm voxels (non-repeating pass)",
@@ -723,16 +787,6 @@ def main():
                "dtype": "f32", "data": "synthetic", "config": {"workload": out["workload"]}, "flythrough": out}
         print(json.dumps(out))
         return
-    if a.config == "bigmap":
-        a.cam, a.voxel = "l515_720p", 0.002
-        if a.frames_per_step == 90:
-            a.frames_per_step = 240      # 120 frames of a 1 degree/frame sweep, there and back
-        if a.steps == 60:
-            a.steps, a.warmup, a.reps = 2, 1, 3
-        if a.cpu_frames == 1080:
-            a.cpu_frames = 8             # parity on the first frames only (the CPU runs ~30 frames/s)
-        a.host_frames = 0
-        a.streams = 0
     if a.shard and grouped:   # BASELINE configs[3]: one stream, N subvolumes, frames broadcast from rank 0
         out = bench_sharded_stream(a, rank, world, dev, dev_index, backend, torch, dist, ratsdf)
         if rank == 0:
@@ -873,6 +927,7 @@ def main():
         eng.profile_enable(False)
     tot = eng.totals()
     stats = eng.last_frame_stats()
+    dumped = dump_outputs(eng, a.dump_outputs) if (a.dump_outputs and rank == 0) else None
 
     # host cost of enqueueing a frame, measured on an IDLE queue (short bursts, synchronised in
     # between): while the GPU is the bottleneck a long enqueue loop only measures the back-pressure
@@ -1024,6 +1079,8 @@ def main():
             "flythrough": flythrough,
             "parity": parity,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         print(json.dumps(out))
     eng.close()
     if grouped:

@@ -2,7 +2,9 @@
 
     make -C oracle ref                                  # compiles third_party/scannet + stb_image from
                                                         # /root/reference into oracle/_ref/ (git-ignored)
-    python tests/golden/make_sens_ref_golden.py         # writes tests/golden/sens_ref_*.npz
+    python tests/golden/make_sens_ref_golden.py         # writes tests/golden/sens_ref_*.npz, tiny_sens_ref.npz
+                                                        # and sens_stream_ref.json
+    python tests/golden/make_sens_ref_golden.py streams # sens_stream_ref.json + sens_stream_jpeg.npz only
 
 For every variant below a small synthetic .sens stream is written (tests/make_sens.py: PIL-encoded JPEG
 colour, zlib depth), decoded by oracle/_ref/ref_sens_dump -- ml::SensorData::decompressColorAlloc /
@@ -12,7 +14,11 @@ what the reference returned for it is stored as one .npz.  The SSE2 build (what 
 reference runs) and the STBI_NO_SIMD build must agree byte for byte, else the script stops.
 tests/test_sens_reader.py::test_reference_loader_fixtures then feeds the stored streams to
 ra-slam_amd/host's reader and compares bytes.  Fixtures are data: stream in, decoded arrays out.
+The fresh streams of the other reader tests (tests/make_sens.py pinned_streams()) are pinned by their JPEG
+payloads (sens_stream_jpeg.npz) and, by checksum, what the reference's loader returned for them
+(sens_stream_ref.json: per frame the payload's crc32, the colour's shape and crc32, the 16-bit depth's crc32).
 """
+import json
 import subprocess
 import sys
 import tempfile
@@ -61,6 +67,9 @@ def main():
     if not (REF / "ref_sens_dump").exists():
         raise SystemExit("oracle/_ref/ref_sens_dump missing: run `make -C oracle ref` where /root/reference exists")
     out_dir = ROOT / "tests" / "golden"
+    if sys.argv[1:] == ["streams"]:
+        write_stream_pins(out_dir)
+        return
     for name, (n, hw, kw, gray) in VARIANTS.items():
         with tempfile.TemporaryDirectory() as td:
             td = Path(td)
@@ -103,6 +112,33 @@ def main():
                             depth_crc=np.array([zlib.crc32(d.tobytes()) for d in depth], dtype=np.uint64),
                             **{f"color{i}": c for i, c in enumerate(color)})
         print("tiny.sens      ->  tiny_sens_ref.npz")
+    write_stream_pins(out_dir)
+
+
+def write_stream_pins(out_dir):
+    """the fresh streams of test_sens_reader.py: JPEG payloads, and the reference's decode by checksum"""
+    pins, payloads = {}, {}
+    for key, (n, hw, seed, kw) in M.pinned_streams().items():
+        with tempfile.TemporaryDirectory() as td:
+            td = Path(td)
+            frames = M.synthetic_frames(n, color_hw=hw, seed=seed)
+            sens = td / "s.sens"
+            jpeg = [M.encode_jpeg(f["rgb"], **kw) for f in frames]
+            M.write_sens(sens, frames, color_payloads=jpeg)
+            color, depth, _, _ = run_ref(REF / "ref_sens_dump", sens, td / "simd")
+            color_s, depth_s, _, _ = run_ref(REF / "ref_sens_dump_scalar", sens, td / "scalar")
+            for a, b in zip(color + depth, color_s + depth_s):
+                if not np.array_equal(a, b):
+                    raise SystemExit(f"{key}: stb's SSE2 and scalar builds disagree")
+            payloads.update({M.payload_name(key, i): np.frombuffer(j, dtype=np.uint8) for i, j in enumerate(jpeg)})
+            pins[key] = dict(jpeg_crc=[zlib.crc32(j) for j in jpeg],
+                             color_shape=[list(c.shape) for c in color],
+                             color_crc=[zlib.crc32(c.tobytes()) for c in color],
+                             depth_crc=[zlib.crc32(d.tobytes()) for d in depth])
+    (out_dir / "sens_stream_ref.json").write_text(      # one stream per line
+        "{\n" + ",\n".join(f" {json.dumps(k)}: {json.dumps(pins[k], sort_keys=True)}" for k in sorted(pins)) + "\n}\n")
+    np.savez_compressed(out_dir / "sens_stream_jpeg.npz", **payloads)
+    print(f"{len(pins)} fresh streams  ->  sens_stream_ref.json, sens_stream_jpeg.npz")
 
 
 if __name__ == "__main__":

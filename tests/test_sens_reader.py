@@ -5,14 +5,17 @@ stb_image.h, compiled from /root/reference into oracle/_ref/ref_sens_dump (`make
 container only).  What it decodes from small synthetic streams is committed as tests/golden/sens_ref_*.npz
 and tiny_sens_ref.npz (tests/golden/make_sens_ref_golden.py): colour bytes BEFORE cv::resize, 16-bit
 depth, stored poses, calibration.  The reader must reproduce them byte for byte
-(test_reference_loader_fixtures: runs anywhere).  The remaining tests write fresh streams and compare
-with the reference loader run on the spot, so they need oracle/_ref (skipped where it is absent).
+(test_reference_loader_fixtures: runs anywhere).  The remaining tests write fresh streams
+(tests/make_sens.py pinned_streams()) from the JPEG payloads stored in tests/golden/sens_stream_jpeg.npz and
+compare with what the reference loader decoded from them, stored by checksum in tests/golden/sens_stream_ref.json.
 After the decode, cv::resize's 8-bit bilinear kernel is checked against its numpy restatement
 (oracle/segmentation_oracle.py; parity unpinned: no OpenCV in this image) and SE3::Inverse against
 ratsdf.pose (Eigen restated)."""
 import io
+import json
 import subprocess
 import sys
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -23,6 +26,7 @@ HOST = ROOT / "ra-slam_amd" / "host"
 EXE = HOST / "build" / "ratsdf_offline_eval"
 sys.path.insert(0, str(ROOT / "oracle"))
 sys.path.insert(0, str(ROOT / "tests"))
+import make_sens as M  # noqa: E402
 
 
 def build():
@@ -30,8 +34,8 @@ def build():
     return EXE
 
 
-REF_EXE = ROOT / "oracle" / "_ref" / "ref_sens_dump"
-needs_ref = pytest.mark.skipif(not REF_EXE.exists(), reason="oracle/_ref not built (no reference tree here)")
+STREAM_PINS = json.loads((ROOT / "tests" / "golden" / "sens_stream_ref.json").read_text())
+STREAM_JPEG = np.load(ROOT / "tests" / "golden" / "sens_stream_jpeg.npz")
 
 
 def dump(sens, tmp):
@@ -52,14 +56,25 @@ def dump(sens, tmp):
     return meta, rgb, depth, poses, raw
 
 
-def reference_loader(sens, tmp):
-    """the reference's own loader on the same stream: colour before the resize, 16-bit depth"""
-    tmp.mkdir(parents=True, exist_ok=True)
-    subprocess.run([str(REF_EXE), str(sens), str(tmp)], check=True, timeout=120)
-    cw, ch, dw, dh, n = (int(v) for v in (tmp / "meta.txt").read_text().split()[:5])
-    color = [np.fromfile(tmp / f"{i}.color", dtype=np.uint8).reshape(ch, cw, 3) for i in range(n)]
-    depth = [np.fromfile(tmp / f"{i}.depth", dtype=np.uint16).reshape(dh, dw) for i in range(n)]
-    return color, depth
+def pinned_stream(key, path):
+    """writes the fresh stream `key` (stored JPEG colour, depth and poses of synthetic_frames) -> (frames, what the
+    reference's loader decoded from it: per frame the colour shape and crc32 of the colour before the resize and of
+    the 16-bit depth)"""
+    n, hw, seed, _ = M.pinned_streams()[key]
+    frames = M.synthetic_frames(n, color_hw=hw, seed=seed)
+    jpeg = [STREAM_JPEG[M.payload_name(key, i)].tobytes() for i in range(n)]
+    pin = STREAM_PINS[key]
+    assert [zlib.crc32(j) for j in jpeg] == pin["jpeg_crc"], f"{key}: stored JPEG payloads != the pinned ones"
+    M.write_sens(path, frames, color_payloads=jpeg)
+    return frames, pin
+
+
+def assert_colour_pinned(raw, pin, what):
+    """the reader's colour before the resize == the reference loader's, byte for byte (by crc32)"""
+    for i, c in enumerate(raw):
+        assert list(c.shape) == pin["color_shape"][i], (what, i, c.shape)
+        assert zlib.crc32(c.tobytes()) == pin["color_crc"][i], \
+            f"{what} frame {i}: decoded colour differs from the reference loader's"
 
 
 def expected_pose(c2w):
@@ -69,13 +84,16 @@ def expected_pose(c2w):
 
 
 def check_stream(frames, ref_color, meta, rgb, depth, poses, raw, depth_shift=1000.0):
+    """ref_color: the colour before the resize the reader must have decoded (None: f["rgb"], raw colour streams);
+    raw=None when the caller has already checked the decoded colour (assert_colour_pinned) and passes it as ref_color"""
     import segmentation_oracle as O
     assert (meta["width"], meta["height"], meta["n"]) == (640, 480, len(frames))
     assert np.allclose(meta["extrinsics"], [0, 0, 0, 1, 0, 0, 0])
     for i, f in enumerate(frames):
         full = ref_color[i] if ref_color is not None else f["rgb"]
-        assert np.array_equal(raw[i], full), f"frame {i}: decoded colour differs from the reference loader's " \
-            f"in {int((raw[i] != full).sum())} bytes (max {int(np.abs(raw[i].astype(int) - full.astype(int)).max())})"
+        if raw is not None:
+            assert np.array_equal(raw[i], full), f"frame {i}: decoded colour differs from the reference loader's " \
+                f"in {int((raw[i] != full).sum())} bytes (max {int(np.abs(raw[i].astype(int) - full.astype(int)).max())})"
         want = O.resize_u8_linear(full, 480, 640)
         assert np.array_equal(rgb[i], want), f"frame {i}: colour differs by up to " \
             f"{int(np.abs(rgb[i].astype(int) - want.astype(int)).max())}"
@@ -85,50 +103,39 @@ def check_stream(frames, ref_color, meta, rgb, depth, poses, raw, depth_shift=10
         assert np.allclose(poses[i], expected_pose(f["cam_to_world"]), atol=1e-6)
 
 
-@needs_ref
-@pytest.mark.parametrize("subsampling,restart,quality", [("4:2:0", 0, 88), ("4:2:2", 0, 88), ("4:4:4", 0, 88),
-                                                         ("4:2:0", 2, 88), ("4:1:1", 0, 75), ("4:2:0", 1, 25),
-                                                         ("4:2:2", 3, 100)])
+@pytest.mark.parametrize("subsampling,restart,quality", M.JPEG_VARIANTS)
 def test_sens_stream_jpeg_variants(tmp_path, subsampling, restart, quality):
-    """fresh streams, reference loader run on the spot (build container)"""
-    import make_sens as M
-    frames = M.synthetic_frames(2, color_hw=(121, 163), seed=quality)   # odd sizes: partial MCUs, odd chroma edge
-    kw = dict(quality=quality, subsampling=subsampling, restart_rows=restart)
+    """fresh streams (odd sizes: partial MCUs, odd chroma edge) against the reference loader's decode"""
+    key = M.jpeg_variant_key(subsampling, restart, quality)
     sens = tmp_path / "s.sens"
-    M.write_sens(sens, frames, jpeg_kw=kw)
-    ref_color, ref_depth = reference_loader(sens, tmp_path / "ref")
+    frames, pin = pinned_stream(key, sens)
     meta, rgb, depth, poses, raw = dump(sens, tmp_path / "dump")
     assert np.allclose(meta["intrinsics"], [577.87, 577.87, 319.5, 239.5])
     assert meta["factor"] == np.float32(1000.0)
-    check_stream(frames, ref_color, meta, rgb, depth, poses, raw)
+    assert_colour_pinned(raw, pin, key)
+    check_stream(frames, raw, meta, rgb, depth, poses, None)   # raw == the reference's colour: checked just above
     for i, f in enumerate(frames):
-        assert np.array_equal(ref_depth[i], f["depth"])      # (stb's inflate == zlib's, as it must)
+        assert zlib.crc32(f["depth"].tobytes()) == pin["depth_crc"][i]   # (stb's inflate == zlib's, as it must)
 
 
-@needs_ref
-@pytest.mark.parametrize("hw", [(1, 1), (1, 9), (9, 1), (2, 3), (8, 8), (16, 16), (17, 33), (15, 31)])
+@pytest.mark.parametrize("hw", M.EDGE_SIZES)
 def test_sens_stream_small_and_edge_sizes(tmp_path, hw):
     """one-sample chroma rows / columns, images smaller than an MCU, exact and inexact MCU multiples"""
-    import make_sens as M
-    for k, sub in enumerate(("4:2:0", "4:2:2", "4:4:4", "4:1:1")):
-        frames = M.synthetic_frames(1, color_hw=hw, seed=5 + k)
+    for k, sub in enumerate(M.EDGE_SUBSAMPLINGS):
+        key = M.edge_key(hw, sub)
         sens = tmp_path / f"s{k}.sens"
-        M.write_sens(sens, frames, jpeg_kw=dict(quality=93, subsampling=sub))
-        ref_color, _ = reference_loader(sens, tmp_path / f"ref{k}")
+        _, pin = pinned_stream(key, sens)
         raw = dump(sens, tmp_path / f"dump{k}")[4]
-        assert np.array_equal(raw[0], ref_color[0]), (hw, sub)
+        assert_colour_pinned(raw[:1], pin, (hw, sub))
 
 
-@needs_ref
 def test_sens_stream_scannet_sized_colour(tmp_path):
     """1296 x 968 colour (the ScanNet recorder's size) resized to 640 x 480."""
-    import make_sens as M
-    frames = M.synthetic_frames(1, color_hw=(968, 1296))
     sens = tmp_path / "s.sens"
-    M.write_sens(sens, frames, jpeg_kw=dict(quality=92))
-    ref_color, _ = reference_loader(sens, tmp_path / "ref")
+    frames, pin = pinned_stream("scannet_colour", sens)
     meta, rgb, depth, poses, raw = dump(sens, tmp_path / "dump")
-    check_stream(frames, ref_color, meta, rgb, depth, poses, raw)
+    assert_colour_pinned(raw, pin, "scannet_colour")
+    check_stream(frames, raw, meta, rgb, depth, poses, None)   # raw == the reference's colour: checked just above
 
 
 FIXTURES = sorted(p.name for p in (ROOT / "tests" / "golden").glob("sens_ref_*.npz"))
