@@ -1,0 +1,60 @@
+/*
+ * ratsdf_map.h -- map checkpoints of the HIP engine: save an engine's map to a file and resume it exactly.
+ *
+ * Kept apart from ratsdf.h because the CPU oracle does not implement these entry points (the reference has no
+ * TSDF load path at all).  A map saved after frame A and loaded into an engine of the same
+ * configuration continues bit-exactly: the same directory entries, the same free list in its LIFO order, the
+ * same voxels -- frames A+1 .. produce what an engine that was never interrupted produces.
+ *
+ * File format, version 1 (all fields little-endian; DESIGN.md 3 "Map files"):
+ *   header   64 bytes:
+ *              char     magic[8] = "RATSDFMP"
+ *              uint32   version = 1, header_size = 64
+ *              float32  voxel_size, truncation
+ *              int32    block_bits, bucket_bits, shard_rank, shard_count, shard_slab_bits
+ *              int32    segm_live   (1: the map has seen probabilities -- a frame with ht / lt, or imported blocks)
+ *              int32    num_free, free_low   (free count; its lowest value ever: pool indices below it never used)
+ *              uint32   n_entries, n_blocks
+ *   entries  n_entries x {uint32 entry index, int16 x, y, z, offset, int32 idx}, ascending entry index: every
+ *            entry with idx >= 0 (a block) and every entry with idx = -1 and offset != 0 (a dead chain node)
+ *   heap     num_free x int32: heap[0 : num_free], the free list bottom to top (AquireBlock pops the top);
+ *            heap[i] = i for i < free_low
+ *   voxels   n_blocks x 1536 uint32: {tsdf[512] | rgbw[512] | prob[512]}, voxel order x + 8y + 64z, the blocks of
+ *            the entries with idx >= 0 in entry order
+ *   colour   (num_free - free_low) x 512 uint32: rgbw[512] of the free blocks heap[free_low : num_free], in heap
+ *            order -- blocks that have been in use: AquireBlock leaves a block's colour as found (voxel_mem.cu:43-51),
+ *            so it is part of the map's future.  The never-used blocks below free_low hold colour 0
+ *   trailer  uint64 checksum of every byte before it: FNV-1a over 64-bit words -- the bytes read as consecutive
+ *            little-endian uint64 (the last one zero-padded to 8 bytes); h = 0xcbf29ce484222325, then for each
+ *            word w: h = (h ^ w) * 0x100000001b3 (mod 2^64)
+ *
+ * Every call returns a ratsdf_status: an I/O failure, or a malformed, corrupted or mismatched file, is
+ * RATSDF_ERR_BAD_ARGUMENT.
+ */
+#ifndef RATSDF_MAP_H_
+#define RATSDF_MAP_H_
+
+#include "ratsdf.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Waits for the engine's work (the last frame's deferred pool releases included) and writes the map to
+ * path + ".tmp", renamed to `path` once complete: a failed save leaves an earlier file at `path` as it was.
+ * Refuses with the sticky status if one is set (ratsdf_recover first), and with RATSDF_ERR_DEVICE if the directory
+ * names a pool block twice (such a map cannot be resumed; nothing is written).  The map is not changed. */
+int ratsdf_save_map(ratsdf_engine* e, const char* path);
+/* Validates the whole file on the host first; its voxel size, truncation, table bits and shard fields must equal
+ * the engine's.  Then replaces the engine's map with the file's (no engine buffer is reallocated: captured batch
+ * graphs and groups stay valid), clears a sticky error and tells a consumer of directory deltas to take a whole
+ * directory next.  On refusal the map is unchanged. */
+int ratsdf_load_map(ratsdf_engine* e, const char* path);
+/* Host only -- no device, no engine: validates the whole file, fills cfg's voxel_size, truncation, block_bits,
+ * bucket_bits and shard_* (the other fields are zeroed) and *n_blocks (live blocks).  Either pointer may be NULL. */
+int ratsdf_map_file_info(const char* path, ratsdf_config* cfg, int64_t* n_blocks);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RATSDF_MAP_H_ */

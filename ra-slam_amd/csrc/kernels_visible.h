@@ -16,7 +16,10 @@
 
 namespace ratsdf {
 
-enum SelectMode { kSelVisible = 0, kSelValid = 1, kSelBounds = 2, kSelOwned = 3 };
+// kSelStored (map files, mapfile.inc): every entry a checkpoint must keep -- the live ones and the dead chain nodes
+// (idx < 0, offset != 0) that lookups walk over.  An entry with idx < 0 and offset 0 is empty whatever its position
+// words hold (entry_matches needs idx >= 0, a chain walk stops at offset 0), so it is left out.
+enum SelectMode { kSelVisible = 0, kSelValid = 1, kSelBounds = 2, kSelOwned = 3, kSelStored = 4 };
 
 struct GridBounds {  // BoundingCube<short>, voxel_tsdf.cuh:19-34
   int16_t xmin, xmax, ymin, ymax, zmin, zmax;
@@ -38,6 +41,13 @@ __device__ inline void select_flags_role(const Table& tab, const FrameParams& P,
   unsigned long long sel = 0;
   if (Mode == kSelValid) {
     sel = occ;                                                              // voxel_tsdf.cu:28-33
+  } else if (Mode == kSelStored) {
+    // (dead chain nodes have no occupancy bit: every entry of the word is read -- 768 bytes per lane, once per save)
+    if (w < nwords)
+      for (int b = 0; b < 64; ++b) {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(tab.entries + ((size_t)w * 64 + b));
+        if ((int32_t)p[2] >= 0 || (p[1] >> 16) != 0u) sel |= 1ull << b;
+      }
   } else {
     while (occ) {
       const int b = __ffsll((long long)occ) - 1;

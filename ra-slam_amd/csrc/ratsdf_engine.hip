@@ -631,6 +631,9 @@ int ratsdf_engine::select(int mode, const GridBounds& gb, uint32_t* count_slot) 
   else if (mode == kSelOwned)
     hipLaunchKernelGGL(k_select_flags<kSelOwned>, dim3(nwg), dim3(kVisWG), 0, stream, tab, P, gb,
                        masks, wg_count);
+  else if (mode == kSelStored)
+    hipLaunchKernelGGL(k_select_flags<kSelStored>, dim3(nwg), dim3(kVisWG), 0, stream, tab, P, gb,
+                       masks, wg_count);
   else
     hipLaunchKernelGGL(k_select_flags<kSelBounds>, dim3(nwg), dim3(kVisWG), 0, stream, tab, P, gb,
                        masks, wg_count);
@@ -1644,10 +1647,9 @@ static int mask_positions(ratsdf_engine* e, const uint32_t* mask, size_t n, uint
 // entry names, ascending), the free count and its low-water mark -- the claim tables, both frames' counters, the
 // candidate counters and the delete bitmaps go back to their initial state, a consumer of directory deltas is told to
 // take a whole directory next, and the error is cleared.  The voxels keep what reached them.  No reference counterpart.
-int ratsdf_recover(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+// keep_heap: the free list, the free count and its low-water mark are left as they are (ratsdf_load_map has just
+// written them); otherwise they are rebuilt from the directory, ascending.
+static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   HIPCHK(hipStreamSynchronize(e->stream));
   if (e->copy_stream) HIPCHK(hipStreamSynchronize(e->copy_stream));
   if (e->copy_stream2) HIPCHK(hipStreamSynchronize(e->copy_stream2));
@@ -1679,18 +1681,20 @@ int ratsdf_recover(ratsdf_engine* e) {
   REC_CHK(hipMemsetAsync(&e->ctl->fr[0], 0, 2 * sizeof(FrameCtl), e->stream));
   hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, unused, 1u, nb);
   hipLaunchKernelGGL(k_recover_scan, dim3((t.num_entry + 255) / 256), dim3(256), 0, e->stream, t, unused);
-  uint32_t n_free = 0;
-  if (mask_positions(e, unused, nb, pos, tiles, d_total, &n_free) != RATSDF_OK) return fail(RATSDF_ERR_DEVICE);
-  hipLaunchKernelGGL(k_recover_heap, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, unused, pos,
-                     e->pool.heap, (int32_t)nb);
-  const int32_t nf = (int32_t)n_free;
-  REC_CHK(hipMemcpyAsync(&e->ctl->num_free, &nf, 4, hipMemcpyHostToDevice, e->stream));
-  // (the low-water mark only ever goes down: slots at or above it may have been in use; the rebuilt heap keeps the
-  // never-used indices -- the lowest ones -- at its bottom, so the mark stays true.  A free count below it moves it.)
-  int32_t low = 0;
-  REC_CHK(hipMemcpyAsync(&low, &e->ctl->free_low, 4, hipMemcpyDeviceToHost, e->stream));
-  REC_CHK(hipStreamSynchronize(e->stream));
-  if (nf < low) REC_CHK(hipMemcpyAsync(&e->ctl->free_low, &nf, 4, hipMemcpyHostToDevice, e->stream));
+  if (!keep_heap) {
+    uint32_t n_free = 0;
+    if (mask_positions(e, unused, nb, pos, tiles, d_total, &n_free) != RATSDF_OK) return fail(RATSDF_ERR_DEVICE);
+    hipLaunchKernelGGL(k_recover_heap, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, unused, pos,
+                       e->pool.heap, (int32_t)nb);
+    const int32_t nf = (int32_t)n_free;
+    REC_CHK(hipMemcpyAsync(&e->ctl->num_free, &nf, 4, hipMemcpyHostToDevice, e->stream));
+    // (the low-water mark only ever goes down: slots at or above it may have been in use; the rebuilt heap keeps the
+    // never-used indices -- the lowest ones -- at its bottom, so the mark stays true.  A free count below it moves it.)
+    int32_t low = 0;
+    REC_CHK(hipMemcpyAsync(&low, &e->ctl->free_low, 4, hipMemcpyDeviceToHost, e->stream));
+    REC_CHK(hipStreamSynchronize(e->stream));
+    if (nf < low) REC_CHK(hipMemcpyAsync(&e->ctl->free_low, &nf, 4, hipMemcpyHostToDevice, e->stream));
+  }
   if (t.delta_on) {  // the delta log no longer describes what changed: the next export reports an overflow
     const uint32_t over = 0x80000000u;
     REC_CHK(hipMemcpyAsync(t.del_count, &over, 4, hipMemcpyHostToDevice, e->stream));
@@ -1705,6 +1709,13 @@ int ratsdf_recover(ratsdf_engine* e) {
   e->cand_ready = false;
   (void)hipFree(tmp);
   return RATSDF_OK;
+}
+
+int ratsdf_recover(ratsdf_engine* e) {
+  DeviceGuard guard(e ? e->device : -1);
+  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  return rebuild_derived(e, false);
 }
 
 int ratsdf_stream(ratsdf_engine* e, void** out) {
@@ -3039,3 +3050,5 @@ int ratsdf_group_profile_read(ratsdf_group* g, double* ms, int64_t* launches) {
 }
 
 }  // extern "C"
+
+#include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)

@@ -38,6 +38,11 @@ struct Api {
   int (*num_active_blocks)(ratsdf_engine*, int32_t*) = nullptr;
   const char* (*status_string)(int) = nullptr;
   const char* (*backend)() = nullptr;
+  // include/ratsdf_map.h: resolved when the library has them (the CPU oracle does not: then nullptr, and the
+  // calls below report RATSDF_ERR_NOT_IMPLEMENTED)
+  int (*save_map)(ratsdf_engine*, const char*) = nullptr;
+  int (*load_map)(ratsdf_engine*, const char*) = nullptr;
+  int (*map_file_info)(const char*, ratsdf_config*, int64_t*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -84,6 +89,10 @@ class TSDFGrid {
   // ratsdf_recover: after a sticky engine error (last_status() != 0 for good) rebuild what is derived from the block
   // directory and clear the error; true when the engine is usable again.  No reference counterpart (it asserts).
   bool Recover();
+  // map checkpoints (include/ratsdf_map.h): the map to a file / the map replaced by a file's, which continues
+  // bit-exactly.  Return the status (also kept in last_status()); no reference counterpart.
+  int SaveMap(const std::string& path);
+  int LoadMap(const std::string& path);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

@@ -143,6 +143,9 @@ class TSDFSystem {
 
   // additions (not in the reference)
   void Flush();                 // block until every queued frame has been integrated
+  // map checkpoints (include/ratsdf_map.h): Flush() first, then under the engine's mutex; return the status
+  int SaveMap(const std::string& path);
+  int LoadMap(const std::string& path);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "../../../../include/ratsdf.h"
+#include "../../../../include/ratsdf_map.h"
 
 namespace ratsdf {
 

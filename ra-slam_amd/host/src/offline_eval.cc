@@ -17,6 +17,8 @@
 //          [--reader-only] [--dump-frames DIR] [--dump-raw-color (.sens: also DIR/<i>.color, the colour
 //          frame before the resize, and DIR/raw_meta.txt = its width and height)]
 //          [--threads N (decoder threads, default 4)]
+//          [--load-map FILE (a map checkpoint to continue, before the first frame; its voxel size must be --voxel)]
+//          [--first-frame K (skip the first K frames of the dataset)] [--save-map FILE (after the last frame)]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -49,8 +51,8 @@ int main(int argc, char** argv) {
   const std::string data_path = argv[1];
   const char* lib = nullptr;
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
-  int device = 0, max_frames = -1, threads = 4;
-  std::string download_all, download_mesh, dump_dir;
+  int device = 0, max_frames = -1, threads = 4, first_frame = 0;
+  std::string download_all, download_mesh, dump_dir, load_map, save_map;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -72,6 +74,9 @@ int main(int argc, char** argv) {
     else if (a == "--dump-frames") dump_dir = next();
     else if (a == "--reader-only") reader_only = true;
     else if (a == "--dump-raw-color") dump_raw_color = true;
+    else if (a == "--load-map") load_map = next();
+    else if (a == "--save-map") save_map = next();
+    else if (a == "--first-frame") first_frame = atoi(next());
     else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
       return 2;
@@ -109,6 +114,24 @@ int main(int argc, char** argv) {
       tsdf = std::make_unique<TSDFSystem>(voxel_size, voxel_size * 6, max_depth, K, ext, device,
                                           &Api::Load(lib));
     fprintf(stderr, "[offline_eval] stream size %d (%dx%d)\n", n, reader.get_width(), reader.get_height());
+    if (tsdf && !load_map.empty()) {  // map checkpoint (include/ratsdf_map.h): the run continues it
+      const Api& api = Api::Load(lib);
+      ratsdf_config cfg;
+      int64_t n_blocks = 0;
+      const int st = api.map_file_info ? api.map_file_info(load_map.c_str(), &cfg, &n_blocks)
+                                       : RATSDF_ERR_NOT_IMPLEMENTED;
+      if (st != RATSDF_OK) {
+        fprintf(stderr, "[offline_eval] --load-map %s: %s\n", load_map.c_str(), api.status_string(st));
+        return 1;
+      }
+      if (cfg.voxel_size != voxel_size) {
+        fprintf(stderr, "[offline_eval] --load-map %s: voxel size %g, --voxel %g\n", load_map.c_str(),
+                cfg.voxel_size, voxel_size);
+        return 1;
+      }
+      if (tsdf->LoadMap(load_map) != RATSDF_OK) return 1;
+      fprintf(stderr, "[offline_eval] loaded %lld blocks from %s\n", (long long)n_blocks, load_map.c_str());
+    }
     std::vector<float> poses;
     double t_read = 0;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -119,6 +142,7 @@ int main(int argc, char** argv) {
       const auto t0 = std::chrono::steady_clock::now();
       if (!source.next(&fr)) break;  // pose, colour frame, depth frame in metres (:69-74)
       t_read += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (frame_idx < first_frame) continue;  // (--first-frame: integrated by the run that saved the map)
       const SE3<float>& cam_T_world = fr.pose;
       const PngImage& rgb = fr.rgb;
       const std::vector<float>& depth = fr.depth;
@@ -142,6 +166,7 @@ int main(int argc, char** argv) {
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
       fprintf(stderr, "[offline_eval] %d frames in %.3f s (%.1f frames/s; waited %.3f s for the decoders)\n", n, dt,
               n / dt, t_read);
+      if (!save_map.empty() && tsdf->SaveMap(save_map) != RATSDF_OK) return 1;
       if (!download_all.empty()) tsdf->DownloadAll(download_all);
       if (!download_mesh.empty())  // offline_eval.cc:95-98
         tsdf->DownloadAllMesh(download_mesh + "_vertices.bin", download_mesh + "_indices.bin",

@@ -73,6 +73,10 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.num_active_blocks = reinterpret_cast<decltype(api.num_active_blocks)>(sym("num_active_blocks"));
   api.status_string = reinterpret_cast<decltype(api.status_string)>(sym("status_string"));
   api.backend = reinterpret_cast<decltype(api.backend)>(sym("backend"));
+  auto opt_sym = [&](const char* name) { return dlsym(api.handle, (std::string(prefix) + name).c_str()); };
+  api.save_map = reinterpret_cast<decltype(api.save_map)>(opt_sym("save_map"));
+  api.load_map = reinterpret_cast<decltype(api.load_map)>(opt_sym("load_map"));
+  api.map_file_info = reinterpret_cast<decltype(api.map_file_info)>(opt_sym("map_file_info"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -204,6 +208,18 @@ bool TSDFGrid::Recover() {
   if (!engine_) return false;
   status_ = api_->recover(engine_);
   return status_ == RATSDF_OK;
+}
+
+int TSDFGrid::SaveMap(const std::string& path) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->save_map ? api_->save_map(engine_, path.c_str()) : RATSDF_ERR_NOT_IMPLEMENTED, "SaveMap");
+  return status_;
+}
+
+int TSDFGrid::LoadMap(const std::string& path) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->load_map ? api_->load_map(engine_, path.c_str()) : RATSDF_ERR_NOT_IMPLEMENTED, "LoadMap");
+  return status_;
 }
 
 int TSDFGrid::NumActiveBlock() {
@@ -451,6 +467,18 @@ void TSDFSystem::Render(const CameraParams& virtual_cam, const SE3<float> cam_T_
                         uint8_t* img_rgba, uint8_t* img_normal, float max_depth) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   tsdf_.RayCast(max_depth, virtual_cam, cam_T_world, img_rgba, img_normal);       // tsdf_module.cc:51-55
+}
+
+int TSDFSystem::SaveMap(const std::string& path) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.SaveMap(path);
+}
+
+int TSDFSystem::LoadMap(const std::string& path) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.LoadMap(path);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

@@ -29,6 +29,13 @@ def library():
     return _lib
 
 
+def map_file_info(path):
+    """Validates a map checkpoint on the host (no device needed) and returns its configuration and the number of live
+    blocks: ``{voxel_size, truncation, block_bits, bucket_bits, shard_rank, shard_count, shard_slab_bits,
+    n_blocks}``.  Raises RatsdfError (status 1) for a malformed or corrupted file."""
+    return library().map_file_info(path)
+
+
 class TSDFGrid(Engine):
     """``TSDFGrid(voxel_size, truncation)`` of utils/tsdf/voxel_tsdf.cuh:47 on one MI355X."""
 
@@ -37,5 +44,5 @@ class TSDFGrid(Engine):
 
 
 __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "Pose", "Bounds",
-           "RatsdfError", "pose_from_matrix", "compose", "invert", "identity_pose", "BLOCK_DTYPE",
+           "RatsdfError", "map_file_info", "pose_from_matrix", "compose", "invert", "identity_pose", "BLOCK_DTYPE",
            "RGBW_DTYPE", "VOXEL_TSDF_DTYPE", "VOXEL_SEGM_DTYPE", "LIB_PATH"]

@@ -5,6 +5,7 @@ oracle (prefix ``ratsdf_oracle_``).  This module only knows the ABI's shape; whi
 and prefix to bind is the caller's choice (the product binds libratsdf.so, see ``__init__``).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -78,6 +79,9 @@ SYMBOLS = [
     "test_retrieve", "test_assign_rgbw", "dump_directory", "dump_voxels", "dump_heap",
     "status_string", "backend",
 ]
+# include/ratsdf_map.h (map checkpoints): bound when the library has them -- the CPU oracle does not, and there the
+# methods raise RatsdfError with status 6 (not implemented)
+MAP_SYMBOLS = ["save_map", "load_map", "map_file_info"]
 
 
 class _OwnedBuffer:
@@ -184,9 +188,26 @@ class Library:
         self.fn["dump_heap"].argtypes = [vp, C.POINTER(C.c_int32), vp]
         self.fn["status_string"].argtypes = [C.c_int]
         self.fn["backend"].argtypes = []
+        for s in MAP_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = {"save_map": [vp, C.c_char_p], "load_map": [vp, C.c_char_p],
+                              "map_file_info": [C.c_char_p, C.POINTER(Config), C.POINTER(C.c_int64)]}[s]
+            self.fn[s] = f
 
     def backend(self):
         return self.fn["backend"]().decode()
+
+    def map_file_info(self, path):
+        """validates a map file on the host (ratsdf_map_file_info): its configuration and number of live blocks"""
+        cfg, n = Config(), C.c_int64()
+        _check(self.fn["map_file_info"](os.fsencode(path), C.byref(cfg), C.byref(n)), "map_file_info")
+        return {"voxel_size": cfg.voxel_size, "truncation": cfg.truncation, "block_bits": cfg.block_bits,
+                "bucket_bits": cfg.bucket_bits, "shard_rank": cfg.shard_rank, "shard_count": cfg.shard_count,
+                "shard_slab_bits": cfg.shard_slab_bits, "n_blocks": n.value}
 
 
 def _check(st, what):
@@ -358,6 +379,14 @@ class Engine:
     def recover(self):
         """after a sticky error: rebuild everything derived from the block directory, clear the error (ratsdf_recover)"""
         _check(self.lib.fn["recover"](self._h), "recover")
+
+    def save_map(self, path):
+        """writes the map to a checkpoint file (ratsdf_save_map, include/ratsdf_map.h)"""
+        _check(self.lib.fn["save_map"](self._h, os.fsencode(path)), "save_map")
+
+    def load_map(self, path):
+        """replaces the map with a checkpoint file's; the map continues bit-exactly (ratsdf_load_map)"""
+        _check(self.lib.fn["load_map"](self._h, os.fsencode(path)), "load_map")
 
     def stream(self):
         s = C.c_void_p()
