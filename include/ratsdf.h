@@ -151,7 +151,8 @@ int ratsdf_integrate_device(ratsdf_engine* e, const void* d_rgb, const void* d_d
                             float max_depth, const ratsdf_intrinsics* intrinsics,
                             const ratsdf_pose* cam_T_world);
 /* n consecutive frames of one stream, all inputs resident in HBM: d_rgb/d_depth/d_ht/d_lt are host
- * arrays of n device pointers (d_ht / d_lt may be NULL = no semantics), intrinsics and cam_T_world
+ * arrays of n device pointers (d_ht / d_lt may be NULL = no semantics; a NULL entry d_ht[i] or d_lt[i] makes
+ * frame i alone TSDF-only, as in the reference, modules/tsdf_module.cc:27-31), intrinsics and cam_T_world
  * are host arrays of n elements.  Equivalent to n calls of ratsdf_integrate_device in order (what the
  * reference's TSDFSystem worker does with its queue, modules/tsdf_module.cc:88-115), without the
  * per-call cost of crossing a language boundary.  HIP engine only. */
@@ -167,8 +168,9 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
 int ratsdf_prepare_device_batch(ratsdf_engine* e, int n, int height, int width);
 /* n consecutive frames from HOST memory: the loop of the reference's TSDFSystem worker over its
  * queued inputs (modules/tsdf_module.cc:88-115), as one call.  rgb/depth/ht/lt are host arrays of n
- * host pointers (ht / lt may be NULL = all-ones images); uploads are enqueued ahead of the frames
- * that use them, frame i+1's map-independent part runs while frame i is integrated.  Like
+ * host pointers (ht / lt may be NULL = all-ones images; so may entry i of either, for frame i alone); uploads
+ * are enqueued ahead of the frames that use them, frame i+1's map-independent part runs while frame i is
+ * integrated.  Like
  * ratsdf_integrate the call returns when the caller's buffers are no longer in use -- pageable images have been
  * copied into the engine's staging ring, page-locked ones have been uploaded -- not when the frames have been
  * integrated: the next call's uploads overlap this call's last kernels, and a device error of these frames is

@@ -149,6 +149,7 @@ class TSDFSystem {
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();
+  size_t batches_integrated();  // engine calls the worker made (each takes every frame queued at the time, up to 32)
   size_t pool_system_allocs() { return pool_.system_allocs(); }   // host_alloc calls of the queue's block pool
   size_t pool_system_frees() { return pool_.system_frees(); }
   size_t pool_pageable_blocks() { return pool_.pageable_blocks(); }  // frames the queue kept in ordinary memory
@@ -180,6 +181,7 @@ class TSDFSystem {
   std::condition_variable cv_pause_;
   bool pause_ = false;
   size_t frames_done_ = 0;
+  size_t batches_done_ = 0;
   std::thread t_;  // declared last: everything above exists before Run() starts (tsdf_module.h:144-164)
 };
 

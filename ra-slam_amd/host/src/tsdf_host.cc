@@ -549,6 +549,7 @@ void TSDFSystem::Run() {
       std::lock_guard<std::mutex> lock(mtx_queue_);
       busy_ = false;
       frames_done_ += batch.size();
+      ++batches_done_;
       idle = inputs_.empty();
     }
     cv_queue_.notify_all();
@@ -605,6 +606,11 @@ int TSDFSystem::NumActiveBlock() {
 size_t TSDFSystem::frames_integrated() {
   std::lock_guard<std::mutex> lock(mtx_queue_);
   return frames_done_;
+}
+
+size_t TSDFSystem::batches_integrated() {
+  std::lock_guard<std::mutex> lock(mtx_queue_);
+  return batches_done_;
 }
 
 }  // namespace ratsdf

@@ -362,7 +362,9 @@ class Engine:
                     keep.append(a)
                     ptrs.append(a.ctypes.data)
             return (C.c_void_p * n)(*ptrs)
-        sem = all(f.get("ht") is not None and f.get("lt") is not None for f in frames)
+        # semantics are decided frame by frame (tsdf_module.cc:27-31): the tables go whenever ANY frame has both
+        # images, with NULL entries for the frames that lack one; NULL tables only when no frame has them
+        sem = any(f.get("ht") is not None and f.get("lt") is not None for f in frames)
         h, w = frames[0]["depth"].shape
         ks = (Intrinsics * n)(*[_as_intr(f["intrinsics"]) for f in frames])
         ps = (Pose * n)(*[_as_pose(f["pose"]) for f in frames])

@@ -203,9 +203,11 @@ class FrameCaster:
             off = buf.data_ptr() + np.arange(n, dtype=np.int64) * st
             ch.d_depth = off.tolist()
             ch.d_rgb = (off + rgb_off).tolist()
-            sem = self.semantic and all(ch.has_sem)
-            ch.d_ht = (off + npix * 4).tolist() if sem else None
-            ch.d_lt = (off + npix * 8).tolist() if sem else None
+            # per frame, like the host path: a TSDF-only frame gets NULL entries, never the zero-filled ht / lt of
+            # its slot (ht = lt = 0 would make its probability update NaN)
+            if self.semantic and any(ch.has_sem):
+                ch.d_ht = [int(o) + npix * 4 if s else None for o, s in zip(off, ch.has_sem)]
+                ch.d_lt = [int(o) + npix * 8 if s else None for o, s in zip(off, ch.has_sem)]
         if verify:
             for i in range(n):
                 img = buf[i * st:i * st + rgb_off + npix * 3]

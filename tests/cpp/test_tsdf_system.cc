@@ -267,6 +267,55 @@ int main(int argc, char** argv) {
     CHECK(same(sys.Query(all), ref.GatherVoxels(all)));
   }
 
+  // 10: semantics are decided frame by frame (tsdf_module.cc:27-31), inside the worker's batches too.  A stream of
+  // S, N, S, H frames (S: ht and lt; N: neither; H: ht only, TSDF-only by the same rule), each with ht / lt of its own,
+  // pushed faster than the worker takes it: the worker drains it in batches of several frames, and every two
+  // neighbouring frames differ in kind.  The map -- probabilities included -- is the frame-by-frame one.
+  {
+    const int n = 48;
+    std::vector<Frame> stream;
+    for (int i = 0; i < n; ++i) {
+      stream.push_back(make_frame(i));
+      Frame& f = stream.back();
+      for (int k = 0; k < W * H; ++k) {
+        f.ht[k] = 0.2f + 0.6f * (float)((k % W + 7 * i) % W) / W;
+        f.lt[k] = 1.f - f.ht[k];
+      }
+    }
+    auto ht = [&](int i) { return i % 4 == 1 ? Image{} : img(stream[(size_t)i].ht); };
+    auto lt = [&](int i) { return i % 2 == 1 ? Image{} : img(stream[(size_t)i].lt); };
+    TSDFSystem sys(vs, tr, md, K, SE3<float>::Identity(), 0, &api);
+    TSDFGrid ref(vs, tr, 0, &api);
+    for (int i = 0; i < n; ++i) {
+      const Frame& f = stream[(size_t)i];
+      sys.Integrate(f.pose, img(f.rgb), img(f.depth), ht(i), lt(i));
+    }
+    for (int i = 0; i < n; ++i) {
+      const Frame& f = stream[(size_t)i];
+      ref.Integrate(img(f.rgb), img(f.depth), ht(i), lt(i), md, K, f.pose);
+    }
+    sys.Flush();
+    CHECK(sys.frames_integrated() == (size_t)n);
+    printf("mixed stream: %d frames in %zu batches\n", n, sys.batches_integrated());
+    CHECK(sys.batches_integrated() < (size_t)n);  // some batch held several frames: both kinds side by side
+    const BoundingCube<float> all{-10, 10, -10, 10, -10, 10};
+    CHECK(same(sys.Query(all), ref.GatherVoxels(all)));
+    const char* path = "/tmp/ratsdf_host_test_mixed.bin";
+    sys.DownloadAll(path);
+    const std::vector<VoxelSpatialTSDFSEGM> want = ref.GatherValidSemantic();
+    FILE* fp = fopen(path, "rb");
+    CHECK(fp != nullptr);
+    std::vector<VoxelSpatialTSDFSEGM> got(want.size());
+    CHECK(fread(got.data(), sizeof(VoxelSpatialTSDFSEGM), got.size(), fp) == got.size());
+    CHECK(fgetc(fp) == EOF);
+    fclose(fp);
+    remove(path);
+    CHECK(!want.empty() && memcmp(got.data(), want.data(), want.size() * sizeof(VoxelSpatialTSDFSEGM)) == 0);
+    size_t moved = 0;
+    for (auto& r : want) moved += r.prob != 0.5f;
+    CHECK(moved > want.size() / 4);  // the semantic frames did update the probability
+  }
+
   // bad arguments are reported, not fatal (the reference only asserts)
   {
     TSDFGrid g(vs, tr, 0, &api);

@@ -28,6 +28,9 @@ torch.cuda.set_device(dev)
 dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
 vs, md, C = 0.02, 4.0, 3
 stream = synthetic.stream('room', 11, scale=0.25, noise=True, holes=True)   # 3 chunks + a tail of 2: the ring of 2 wraps
+if %(pattern)r:   # every chunk mixes frames with semantics and TSDF-only ones (tests/mixed_cases.py)
+    from mixed_cases import apply, semantic_frames
+    stream = apply(semantic_frames('room', 11), %(pattern)r)
 H, W = stream[0]['depth'].shape
 gpu = ratsdf.TSDFGrid(vs, 6 * vs)
 cpu = Engine(load_oracle(), vs, 6 * vs)
@@ -64,13 +67,25 @@ print('FRAMECAST_NCCL_OK', w['tsdf'], w['prob'])
 """
 
 
-@pytest.mark.gpu
-def test_device_path_under_the_nccl_backend():
+def _run_child(pattern=""):
     import socket
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    r = subprocess.run([sys.executable, "-c", CODE % dict(root=str(ROOT), port=port)], capture_output=True, text=True,
-                       timeout=300, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, "-c", CODE % dict(root=str(ROOT), port=port, pattern=pattern)],
+                       capture_output=True, text=True, timeout=300, cwd=str(ROOT))
     assert r.returncode == 0 and "FRAMECAST_NCCL_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+@pytest.mark.gpu
+def test_device_path_under_the_nccl_backend():
+    _run_child()
+
+
+@pytest.mark.gpu
+def test_device_path_keeps_semantics_per_frame():
+    """chunks that mix frames with semantics and TSDF-only frames: the device path's ht / lt tables carry NULL for the
+    TSDF-only frames (not the zero-filled ht / lt of their wire slots) and the images of the others"""
+    from mixed_cases import FRAMECAST
+    _run_child(FRAMECAST)

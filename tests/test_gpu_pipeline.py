@@ -452,8 +452,9 @@ def test_host_frames_of_alternating_sizes_without_waiting(make_engine, make_orac
 
 def test_pinned_batches_upload_runs_of_side_by_side_frames(make_engine, make_oracle):
     """ratsdf_integrate_batch(pinned): frames whose page-locked blocks lie side by side at the staging ring's stride
-    (16 bytes per pixel) go up several per copy; blocks elsewhere, frames without semantics and a mixture of both
-    take the per-frame copies.  40 frames per call: the 16-slot ring wraps twice.  Same map as the oracle's."""
+    (16 bytes per pixel) go up several per copy; blocks elsewhere and frames without semantics take the per-frame
+    copies.  40 frames per call: the 16-slot ring wraps twice.  Same map as the oracle's.  (Calls that mix frames with
+    and without semantics: tests/test_gpu_mixed_semantics.py::test_pinned_host_batch_breaks_runs_at_tsdf_only_frames.)"""
     vs, md = 0.02, 4.0
     gpu, cpu = make_engine(vs, 6 * vs), make_oracle(vs, 6 * vs)
     frames = synthetic.stream("room", 40, scale=0.25, noise=True, holes=True)
@@ -543,7 +544,7 @@ def test_tsdf_only_frames_skip_the_probability_only_while_it_is_untouched(make_e
     dev_all = device_frames(frames)
     for lo, hi in ((0, 3), (3, 6), (6, 12)):    # batch 2 = one TSDF-only frame, then two with semantics
         chunk = seq[lo:hi]
-        for i, f in enumerate(chunk):          # (a batch has one semantics setting: frame by frame where it is mixed)
+        for i, f in enumerate(chunk):          # (frame by frame here; mixed batches: tests/test_gpu_mixed_semantics.py)
             d = dev_all[lo + i]
             sem = f["ht"] is not None
             gpu.integrate_device(d["rgb"].data_ptr(), d["depth"].data_ptr(), d["ht"].data_ptr() if sem else 0,

@@ -495,9 +495,13 @@ def _framecast_worker(rank, world, port, ret):
         lib = load_oracle()
         vs, md, C = 0.02, 4.0, 3
         kw = dict(shard_rank=rank, shard_count=world, shard_slab_bits=1)
+        from mixed_cases import apply, semantic_frames
         stream = synthetic.stream("room", 8, scale=0.25, noise=True, holes=True)   # 8 frames: 2 chunks + a tail of 2
         H, W = stream[0]["depth"].shape
-        for semantic in (True, False):
+        mixed = "SNSSNHSN"   # semantics frame by frame inside every chunk, in the wire format with semantics
+        for mode in ("semantic", "tsdf-only", "mixed"):
+            semantic = mode != "tsdf-only"
+            frames = apply(semantic_frames("room", 8), mixed) if mode == "mixed" else stream
             eng = Engine(lib, vs, 6 * vs, **kw)
             fc = framecast.FrameCaster(H, W, C, ring=2, src=0, semantic=semantic)
             assert fc.frames_ahead == C
@@ -506,7 +510,7 @@ def _framecast_worker(rank, world, port, ret):
             for c in range(n_chunks):
                 packed = None
                 if rank == 0:   # only the camera's rank touches the stream
-                    fr = stream[c * C:(c + 1) * C]
+                    fr = frames[c * C:(c + 1) * C]
                     if not semantic:
                         fr = [dict(f, ht=None, lt=None) for f in fr]
                     packed = torch.from_numpy(framecast.pack_chunk(fr, md, H, W, C, first_frame_no=c * C,
@@ -514,13 +518,15 @@ def _framecast_worker(rank, world, port, ret):
                 fc.post(packed)
                 ch = fc.take(verify=True)
                 got_no += ch.frame_no
+                if mode == "mixed":
+                    assert ch.has_sem == [k == "S" for k in mixed[c * C:(c + 1) * C]], ch.has_sem
                 assert ch.max_depth == md and ch.n == min(C, len(stream) - c * C)
                 framecast.integrate_chunk(eng, ch)
                 fc.done(ch)
             assert got_no == list(range(len(stream)))
             assert fc.bytes_sent == n_chunks * framecast.chunk_bytes(H, W, C, semantic)
             direct = Engine(lib, vs, 6 * vs, **kw)
-            for f in stream:
+            for f in frames:
                 direct.integrate(f["rgb"], f["depth"], f["ht"] if semantic else None, f["lt"] if semantic else None,
                                  md, f["intrinsics"], f["pose"])
             w = assert_maps_equal(eng, direct)
