@@ -295,12 +295,11 @@ __device__ inline void log_deleted_positions(const Table& tab, const CarveBufs& 
 // frame have been resolved before this runs (carve_resolve_gate).
 constexpr uint32_t kReleaseWGs = 16;
 
-// `scratch`: 2 * kSmallCarve + 4 words of LDS, 16-byte aligned.
+// `scratch`: 2 * kSmallCarve + 12 words of LDS, 16-byte aligned.
 __device__ inline void carve_release_role(const Table& tab, const Pool& pool, const CarveBufs& cb, Ctl* ctl,
                                           FrameCtl* Fp, uint32_t wg, uint32_t* scratch) {
   uint32_t* del_entry = scratch;
   int32_t* del_pool = reinterpret_cast<int32_t*>(scratch + kSmallCarve);
-  uint32_t& n_extra = scratch[2 * kSmallCarve];
   const uint32_t tid = threadIdx.x, nt = block_threads();
   // one round of loads: counters, free count and (speculatively) the head of the delete list
   const uint32_t pend = Fp->pending;
@@ -311,8 +310,6 @@ __device__ inline void carve_release_role(const Table& tab, const Pool& pool, co
   if (nd > cb.del_cap) nd = cb.del_cap;
   if (ns > cb.slow_cap) ns = cb.slow_cap;
   if (nd + ns > kSmallCarve || nd + ns == 0) return;  // many deletes: carve_finalize does them
-  if (tid == 0) n_extra = 0;
-  __syncthreads();
   if (tid < nd) {
     del_entry[tid] = first.entry;
     del_pool[tid] = first.idx;
@@ -322,16 +319,26 @@ __device__ inline void carve_release_role(const Table& tab, const Pool& pool, co
     del_entry[i] = d.entry;
     del_pool[i] = d.idx;
   }
-  for (uint32_t j = tid; j < ns; j += nt) {  // head / chain deletes that happened: rare
+  // Head / chain deletes that happened (rare), behind the simple ones.  Every release workgroup must file them at
+  // the SAME list positions: the items are shared out among the workgroups by list position below, so an order that
+  // differed between workgroups (an LDS atomicAdd per delete files them in whatever order the waves arrive) would
+  // have one delete's heap slot written twice and another's not at all -- the tail or the serial role then pops a
+  // slot that still holds a pool block in use.  Positions follow j: each thread counts its own, an exclusive scan
+  // over the threads places them.
+  uint32_t mine = 0;
+  for (uint32_t j = tid; j < ns; j += nt) mine += cb.slow[j].state == 2 ? 1u : 0u;
+  uint32_t n_slow_done = 0;
+  uint32_t at = nd + block_exclusive_scan(mine, scratch + 2 * kSmallCarve + 8, &n_slow_done);
+  for (uint32_t j = tid; j < ns; j += nt) {
     const SlowDelete sd = cb.slow[j];
     if (sd.state == 2) {
-      const uint32_t slot = nd + atomicAdd(&n_extra, 1u);
-      del_entry[slot] = sd.entry;
-      del_pool[slot] = sd.freed;
+      del_entry[at] = sd.entry;
+      del_pool[at] = sd.freed;
+      ++at;
     }
   }
   __syncthreads();
-  const uint32_t n = nd + n_extra;
+  const uint32_t n = nd + n_slow_done;
   const uint32_t n64 = (n + 63u) & ~63u;
   if (tid < n64 - n) del_entry[n + tid] = kInf;  // n64 <= kSmallCarve (a multiple of 64)
   __syncthreads();

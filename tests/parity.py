@@ -34,6 +34,35 @@ def assert_heap_equal(a, b):
     assert np.array_equal(ha[:fa], hb[:fb]), "free list contents differ"
 
 
+def assert_pool_consistent(e):
+    """The directory and the free list partition the voxel pool: no pool index is named by two live entries, the
+    free list heap[:num_free] repeats none, free and named indices are disjoint and together make the whole pool, and
+    num_active_blocks() counts the live entries.  Two entries naming one pool block share its voxels and corrupt each
+    other's TSDF without any statistic noticing.  The pool size is the engine's own (1 << block_bits)."""
+    _, blocks = e.dump_directory()
+    nf, heap = e.dump_heap()
+    n_pool = 1 << e.block_bits
+    assert 0 <= nf <= n_pool, f"num_free {nf} outside [0, {n_pool}]"
+    named = blocks["idx"].astype(np.int64)
+    free = np.asarray(heap[:nf], dtype=np.int64)
+    for what, v in (("named", named), ("free", free)):
+        bad = v[(v < 0) | (v >= n_pool)]
+        assert bad.size == 0, f"{what} pool indices outside [0, {n_pool}): {bad[:8].tolist()}"
+    u, c = np.unique(named, return_counts=True)
+    dup = u[c > 1]
+    assert dup.size == 0, (f"{dup.size} pool indices named by two live entries: {dup[:8].tolist()} "
+                           f"(entries {[np.flatnonzero(named == d).tolist() for d in dup[:4]]} of the directory dump)")
+    uf, cf = np.unique(free, return_counts=True)
+    rep = uf[cf > 1]
+    assert rep.size == 0, f"{rep.size} pool indices on the free list twice: {rep[:8].tolist()}"
+    both = np.intersect1d(u, uf)
+    assert both.size == 0, f"{both.size} pool indices both free and named: {both[:8].tolist()}"
+    lost = n_pool - u.size - uf.size
+    assert lost == 0, f"{lost} pool blocks neither free nor named ({u.size} named, {uf.size} free, pool {n_pool})"
+    n_active = e.num_active_blocks()
+    assert n_active == len(named), f"num_active_blocks {n_active} != {len(named)} live entries"
+
+
 def assert_voxels_close(a, b, pool_idx, tol=TOL, chunk=4096):
     worst = dict(tsdf=0.0, prob=0.0)
     for lo in range(0, len(pool_idx), chunk):
@@ -53,6 +82,7 @@ def assert_voxels_close(a, b, pool_idx, tol=TOL, chunk=4096):
 
 
 def assert_maps_equal(a, b, tol=TOL):
+    assert_pool_consistent(a)
     _, blocks = assert_directory_equal(a, b)
     assert_heap_equal(a, b)
     assert a.num_active_blocks() == b.num_active_blocks()
