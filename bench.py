@@ -12,12 +12,16 @@ starts those N ranks itself, as child processes, before it touches the GPU); eac
 (frame-batched config of BASELINE.json) and the ranks all-gather the deltas of their block directories
 over RCCL once per step (ratsdf.multi.DirectoryDeltaExchange).  Rank 0 prints ONE JSON line.
 
-The line also carries
+A plain run does what that line's headline needs and nothing else: it sets up, warms up, times the steps, writes
+`--dump-outputs` if given and prints the line.  The line always carries
   roofline      HBM roofline of the dominant kernel (k_integrate): algorithmic bytes per launch
                 (15 W H + 12 V + 24 U) / its average duration measured with HIP events
                 attached to the dispatch on the engine's stream inside the timed region; `traffic` from
                 the committed PMC passes (`traffic_source`); `launch_also_hosts` = what else rides in
                 that launch; `frame_frac` = the whole frame against the same peak
+`--full` also runs every other leg and check (a plain run prints their keys as null):
+  parity        the HIP map against the CPU oracle's on a bounded prefix of the stream (with --shard: the
+                first received chunk; --config flythrough: the whole pass), asserted before anything is timed
   cpu_baseline  the CPU oracle (multithreaded port; the reference has no CPU path) timed on this
                 box's host cores on a bounded prefix of the same stream (rank 0, N = 1 only), after
                 asserting that it and the HIP engine produce the same map on that prefix
@@ -26,6 +30,8 @@ The line also carries
   multi_stream  S streams of this GPU through one launch pair per frame step (ratsdf_group_*);
                 `value` stays the single-stream number
   host_image_path / pinned_h2d_path   the PCIe-inclusive entry points (never `value`)
+  host_enqueue_us_per_frame, synchronous_frame_path, tsdf_system_path, tsdf_only, flythrough
+                (--config flythrough: the per-frame event passes behind `frame_period_us` / `k_integrate_us`)
 `--config hd2mm | bigmap` run the 1280x720 / 2 mm workload (on a 416 MB map for bigmap) as the main line.
 `--dump-outputs DIR` writes the map the timed steps built as .npy files (dump_outputs()), to compare two builds.
 """
@@ -68,7 +74,8 @@ def parse(argv=None):
     ap.add_argument("--voxel", type=float, default=0.005)
     ap.add_argument("--max-depth", type=float, default=4.0)
     ap.add_argument("--cpu-frames", type=int, default=None,
-                    help="frames of the stream timed on the CPU oracle (0 = skip; default 1080; hd2mm: 60; bigmap: 8)")
+                    help="--full: frames of the stream checked and timed on the CPU oracle (0 = skip; default 1080; "
+                         "hd2mm: 60; bigmap: 8)")
     ap.add_argument("--config", default="vga5mm", choices=["vga5mm", "hd2mm", "bigmap", "flythrough"],
                     help="vga5mm: BASELINE metric config (640x480, 5 mm); hd2mm: 1280x720, 2 mm "
                          "(BASELINE configs[3] workload, single GPU unless --shard); bigmap: hd2mm on a "
@@ -88,19 +95,26 @@ def parse(argv=None):
                     help="N = 1, diagnostic: device memory through PyTorch as for N > 1 (the process then runs on the "
                          "HIP runtime bundled with the PyTorch wheel) -- for same-box comparisons of the two runtimes")
     ap.add_argument("--host-frames", type=int, default=60,
-                    help="frames timed through the host-image entry point, PCIe included (0 = skip)")
+                    help="--full: frames timed through the host-image entry point, PCIe included (0 = skip)")
     ap.add_argument("--sync-every", type=int, default=0,
                     help="diagnostic: host-synchronise every N frames (0 = only at the end)")
     ap.add_argument("--reps", type=int, default=None,
                     help="timed repetitions of the K steps; value = the median repetition (default 5; bigmap: 3)")
     ap.add_argument("--streams", type=int, default=4,
-                    help="N = 1: also time S concurrent streams on this GPU through one launch "
+                    help="--full, N = 1: also time S concurrent streams on this GPU through one launch "
                          "triple per frame step (ratsdf_group_*); 0 / 1 = skip")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="vga5mm, N = 1: skip the bounded 1280x720 / 2 mm legs (`secondary`: hd2mm, bigmap), the "
+                    help="--full, vga5mm, N = 1: skip the bounded 1280x720 / 2 mm legs (`secondary`: hd2mm, bigmap), the "
                          "non-repeating pass (`flythrough`) and the C++ TSDFSystem leg (`tsdf_system_path`)")
     ap.add_argument("--flythrough-frames", type=int, default=None,
-                    help="frames of the non-repeating pass (`flythrough`, default 180; --config flythrough: 360 at 1280x720)")
+                    help="frames of the non-repeating pass (`flythrough` of --full, default 180; --config flythrough: "
+                         "360 at 1280x720)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg and check beside the headline figure (CPU oracle parity and baseline, "
+                         "host-enqueue cost, synchronous and host-image paths, S streams, the 1280x720 legs, the "
+                         "non-repeating pass, TSDFSystem and TSDF-only legs; --shard / --config flythrough: their "
+                         "parity, and flythrough's per-frame event passes); off: set up, warm up, time the steps, "
+                         "dump, print")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the last timed step, write the map as DIR/<name>.npy, float32 / float64, at most 64 MB "
                          "(dump_outputs()): the map of all warm-up and timed steps (warmup + reps x steps), rank 0's "
@@ -419,34 +433,40 @@ def bench_secondary(ratsdf, torch, dev, dev_index, md, cpu_threads, config="hd2m
     return out
 
 
-def bench_flythrough(ratsdf, torch, dev, dev_index, cam, vs, md, nframes, cpu_threads, n_par=12):
+def bench_flythrough(ratsdf, torch, dev, dev_index, cam, vs, md, nframes, cpu_threads, n_par=12, event_passes=True):
     """A non-repeating stream: one pass of the room camera (1 degree / frame, no frame seen twice), from
     an empty map.  Every frame allocates; the first one allocates a whole view (the serial role's long
     path).  Every frame's k_integrate carries events (ratsdf_profile_enable(2)): per-frame kernel time
-    and start-to-start period -> p50 / p99 / max, which a repeating sweep never shows."""
+    and start-to-start period -> p50 / p99 / max, which a repeating sweep never shows.
+    n_par = 0: no parity check; event_passes=False: `frames_per_s` alone (the percentiles and the per-frame
+    figures, which come from passes of their own, are null)."""
     from ratsdf import synthetic
-    from oracle_binding import load_oracle
-    from parity import assert_maps_equal
-    from ratsdf._abi import Engine
     frames = [synthetic.frame("room", i, cam=cam, noise=True, holes=True) for i in range(nframes)]
     H, W = frames[0]["depth"].shape
     d = [{k: torch.from_numpy(f[k]).to(dev) for k in ("rgb", "depth", "ht", "lt")} for f in frames]
     intr = [ratsdf.Intrinsics(*f["intrinsics"]) for f in frames]
     pose = [ratsdf.Pose(*f["pose"]) for f in frames]
-    cpu = Engine(load_oracle(), vs, 6 * vs, threads=cpu_threads)
-    chk = ratsdf.TSDFGrid(vs, 6 * vs, device=dev_index)
     chained = 0   # chained-bucket requests the checked frames sent through the resolver (GPU count)
-    for i, f in enumerate(frames[:n_par]):
-        cpu.integrate(f["rgb"], f["depth"], f["ht"], f["lt"], md, f["intrinsics"], f["pose"])
-        chk.integrate_device(d[i]["rgb"].data_ptr(), d[i]["depth"].data_ptr(), d[i]["ht"].data_ptr(),
-                             d[i]["lt"].data_ptr(), H, W, md, intr[i], pose[i])
-        if n_par > 32:   # a long check: count them (one sync per frame; this engine is not the timed one)
-            chk.synchronize()
-            chained += chk.last_frame_stats()["slow_requests"]
-    chk.synchronize()
-    worst = assert_maps_equal(chk, cpu)
-    chk.close()
-    cpu.close()
+    parity = None
+    if n_par > 0:
+        from oracle_binding import load_oracle
+        from parity import assert_maps_equal
+        from ratsdf._abi import Engine
+        cpu = Engine(load_oracle(), vs, 6 * vs, threads=cpu_threads)
+        chk = ratsdf.TSDFGrid(vs, 6 * vs, device=dev_index)
+        for i, f in enumerate(frames[:n_par]):
+            cpu.integrate(f["rgb"], f["depth"], f["ht"], f["lt"], md, f["intrinsics"], f["pose"])
+            chk.integrate_device(d[i]["rgb"].data_ptr(), d[i]["depth"].data_ptr(), d[i]["ht"].data_ptr(),
+                                 d[i]["lt"].data_ptr(), H, W, md, intr[i], pose[i])
+            if n_par > 32:   # a long check: count them (one sync per frame; this engine is not the timed one)
+                chk.synchronize()
+                chained += chk.last_frame_stats()["slow_requests"]
+        chk.synchronize()
+        worst = assert_maps_equal(chk, cpu)
+        chk.close()
+        cpu.close()
+        parity = dict(frames=n_par, max_abs_tsdf=worst["tsdf"], max_abs_prob=worst["prob"],
+                      directory="bit-exact", chained_bucket_requests=chained if n_par > 32 else None)
     def one_pass(every_frame):
         eng = ratsdf.TSDFGrid(vs, 6 * vs, device=dev_index)
         batch = eng.make_batch([x["rgb"].data_ptr() for x in d], [x["depth"].data_ptr() for x in d],
@@ -475,6 +495,12 @@ def bench_flythrough(ratsdf, torch, dev, dev_index, cam, vs, md, nframes, cpu_th
     #     (scratch and graph are built before the clock starts: ratsdf_prepare_device_batch)
     dts = sorted(one_pass(False)[0] for _ in range(3))
     dt_graph = dts[1]
+    workload = (f"one pass of the 'room' camera, {cam} intrinsics {W}x{H}, voxel {vs * 1e3:g} mm, "
+                f"{nframes} frames, 1 deg / frame, from an empty map (no frame seen twice)")
+    if not event_passes:
+        return dict(workload=workload, frames=nframes, frames_per_s=round(nframes / dt_graph, 1),
+                    frames_per_s_launch_mode="profiling off: the pass is one HIP-graph replay (median of 3 passes, each from an empty map)",
+                    frames_per_s_event_pass=None, frame_period_us=None, k_integrate_us=None, parity=parity)
     # (2) the same pass launched frame by frame with HIP events on every dispatch (ratsdf_profile_enable(2): no
     #     graphs): per-frame k_integrate time and start-to-start period -> the percentiles; its own frames/s is
     #     reported beside them as `frames_per_s_event_pass`
@@ -482,9 +508,7 @@ def bench_flythrough(ratsdf, torch, dev, dev_index, cam, vs, md, nframes, cpu_th
     per = np.sort(period_us[:-1]) if len(period_us) > 1 else np.zeros(1)
     ks = np.sort(k_us)
     q = lambda a, p: float(a[min(len(a) - 1, int(p * len(a)))])
-    return dict(workload=f"one pass of the 'room' camera, {cam} intrinsics {W}x{H}, voxel {vs * 1e3:g} mm, "
-                         f"{nframes} frames, 1 deg / frame, from an empty map (no frame seen twice)",
-                frames=nframes, frames_per_s=round(nframes / dt_graph, 1),
+    return dict(workload=workload, frames=nframes, frames_per_s=round(nframes / dt_graph, 1),
                 frames_per_s_launch_mode="profiling off: the pass is one HIP-graph replay (median of 3 passes, each from an empty map)",
                 frames_per_s_event_pass=round(nframes / dt, 1),
                 percentiles_from="a separate pass launched frame by frame with HIP events on every dispatch (no graphs)",
@@ -501,8 +525,7 @@ def bench_flythrough(ratsdf, torch, dev, dev_index, cam, vs, md, nframes, cpu_th
                 updated_voxels_per_frame=round(tot["updated_voxels"] / max(tot["frames"], 1), 1),
                 allocated_blocks_first_frame=None, active_blocks=stats["active_blocks"],
                 map_voxel_bytes=stats["active_blocks"] * 6144,
-                parity=dict(frames=n_par, max_abs_tsdf=worst["tsdf"], max_abs_prob=worst["prob"],
-                            directory="bit-exact", chained_bucket_requests=chained if n_par > 32 else None),
+                parity=parity,
                 note="period = start of a frame's k_integrate to the start of the next frame's (HIP events "
                      "attached to the dispatches); the first frame allocates a whole view")
 
@@ -567,7 +590,7 @@ def bench_sharded_stream(a, rank, world, dev, dev_index, backend, torch, dist, r
     # ---- parity on the first chunk, from the bytes this rank RECEIVED: transport (byte sums from the camera's
     # rank), then HIP shard == the CPU oracle's shard fed with the same received images
     parity = None
-    if a.cpu_frames > 0:
+    if a.full and a.cpu_frames > 0:
         from oracle_binding import load_oracle
         from parity import assert_maps_equal
         from ratsdf._abi import Engine
@@ -781,7 +804,8 @@ def main():
             raise SystemExit("needs a GPU")
         n = a.flythrough_frames
         out = bench_flythrough(ratsdf, torch, dev, dev_index, "l515_720p", 0.002, a.max_depth, n,
-                               min(len(os.sched_getaffinity(0)), 16), n_par=n)  # parity over the WHOLE pass
+                               min(len(os.sched_getaffinity(0)), 16), n_par=n if a.full else 0,  # parity over the WHOLE pass
+                               event_passes=a.full)
         out = {"metric": "depth+semantic frames/sec integrated @1280x720, 2mm voxels (non-repeating pass)",
                "value": out["frames_per_s"], "unit": "frames/s", "n_gpus": 1, "higher_is_better": True,
                "dtype": "f32", "data": "synthetic", "config": {"workload": out["workload"]}, "flythrough": out}
@@ -814,7 +838,7 @@ def main():
     # ---- parity + CPU baseline on a bounded prefix (rank 0, N = 1) ---------------------------
     cpu_baseline = None
     parity = None
-    if rank == 0 and not grouped and a.cpu_frames > 0:
+    if a.full and rank == 0 and not grouped and a.cpu_frames > 0:
         from oracle_binding import load_oracle
         from parity import assert_maps_equal
         from ratsdf._abi import Engine
@@ -933,7 +957,7 @@ def main():
     # between): while the GPU is the bottleneck a long enqueue loop only measures the back-pressure
     # of the full hardware queue, not the host
     enq_us = None
-    if not a.sync_every:
+    if a.full and not a.sync_every:
         burst = min(16, len(frames))
         small = eng.make_batch([t.data_ptr() for t in d_rgb[:burst]], [t.data_ptr() for t in d_depth[:burst]],
                                [t.data_ptr() for t in d_ht[:burst]], [t.data_ptr() for t in d_lt[:burst]],
@@ -953,8 +977,9 @@ def main():
     # look-ahead candidate pass and no graph -- three launches and a stream synchronisation per frame.  What a tracking
     # loop that needs the map between frames gets; reported separately, never the headline value.
     sync_path = None
-    if rank == 0 and not grouped and not a.sync_every and a.host_frames > 0:   # (--host-frames 0, what the profiling
-        lat = []                                                                # scripts pass: none of the caller-path legs)
+    # (--host-frames 0, what the profiling scripts pass: none of the caller-path legs)
+    if a.full and rank == 0 and not grouped and not a.sync_every and a.host_frames > 0:
+        lat = []
         n_sync = min(4 * len(frames), 360)
         eng.synchronize()
         t_all = time.perf_counter()
@@ -984,7 +1009,7 @@ def main():
     # system ROCm runtime a C / C++ caller links, whatever this process runs on.)
     host_path = None
     pinned_path = None
-    if rank == 0 and not grouped and a.host_frames > 0:
+    if a.full and rank == 0 and not grouped and a.host_frames > 0:
         import subprocess
         r = subprocess.run([sys.executable, str(ROOT / "tools" / "host_paths.py"), "--cam", a.cam, "--scene", a.scene,
                             "--voxel", str(vs), "--max-depth", str(a.max_depth), "--frames", str(len(frames)),
@@ -998,7 +1023,7 @@ def main():
 
     # ---- S streams on this GPU through one launch triple per frame step ------------------------
     multi = None
-    if rank == 0 and not grouped and a.streams > 1 and not a.shard:
+    if a.full and rank == 0 and not grouped and a.streams > 1 and not a.shard:
         multi = bench_streams(ratsdf, torch, dev, dev_index, a.streams, a.scene, a.cam, vs, a.max_depth,
                               min(60, len(frames)), max(a.steps // 2, 4), 3,
                               cpu_threads=min(len(os.sched_getaffinity(0)), 16))
@@ -1008,7 +1033,7 @@ def main():
     flythrough = None
     system_path = None
     tsdf_only = None
-    if rank == 0 and not grouped and a.config == "vga5mm" and not a.no_secondary and a.cpu_frames > 0:
+    if a.full and rank == 0 and not grouped and a.config == "vga5mm" and not a.no_secondary and a.cpu_frames > 0:
         avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         nthr = min(avail, int(os.environ.get("RATSDF_CPU_THREADS", "16")))
         secondary = [bench_secondary(ratsdf, torch, dev, dev_index, a.max_depth, nthr, "hd2mm"),

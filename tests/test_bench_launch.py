@@ -57,9 +57,10 @@ def test_one_stream_over_two_subvolume_ranks_through_the_plain_entry_point(tmp_p
     """BASELINE configs[3] end to end through `python bench.py --gpus 2 --shard`: rank 0 owns the stream, the frames
     reach rank 1 by broadcast (inside the timed region), each rank integrates its subvolume (checked against the
     sharded CPU oracle on the bytes it received), the directory deltas are all-gathered, and every block of the
-    union sits on its owner and nowhere else.  Both ranks on the one device, gloo instead of RCCL."""
+    union sits on its owner and nowhere else.  Both ranks on the one device, gloo instead of RCCL.  (The parity check
+    is part of --full.)"""
     r = _run(["--gpus", "2", "--shard", "--steps", "2", "--warmup", "1", "--reps", "1", "--frames-per-step", "12",
-              "--bcast-chunk", "4", "--cpu-frames", "4", "--dump-outputs", str(tmp_path / "out")],
+              "--bcast-chunk", "4", "--cpu-frames", "4", "--full", "--dump-outputs", str(tmp_path / "out")],
              {"RATSDF_BENCH_DEVICE": "0", "RATSDF_BENCH_BACKEND": "gloo"}, 600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -90,7 +91,8 @@ def test_the_multi_rank_code_path_over_rccl_with_a_group_of_one(mode):
     device_id=...), the directory exchange on device tensors (all_gather_into_tensor), barrier, all_reduce(MAX) of the
     step time -- and, with --shard, the frame broadcast on its side stream and all_gather_object of the shard table."""
     args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reps", "1", "--frames-per-step", "12", "--cpu-frames", "4"]
-    args += ["--shard", "--bcast-chunk", "4"] if mode == "shard" else ["--host-frames", "0", "--no-secondary", "--streams", "0"]
+    args += ["--shard", "--bcast-chunk", "4", "--full"] if mode == "shard" else ["--host-frames", "0", "--no-secondary",
+                                                                                  "--streams", "0"]
     r = _run(args, {"RATSDF_BENCH_ONE_RANK_GROUP": "1"}, 600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -188,6 +190,51 @@ def test_bench_dump_outputs_is_the_map_of_the_timed_steps(tmp_path):
     assert np.max(np.abs(d["tsdf"] - tsdf)) <= 1e-4 and np.max(np.abs(d["prob"] - prob)) <= 1e-4
     assert np.array_equal(d["weight"], rgbw["weight"].astype(np.float32))
     assert np.array_equal(d["rgb"], np.stack([rgbw["r"], rgbw["g"], rgbw["b"]], axis=-1).astype(np.float32))
+
+
+FULL_ONLY_KEYS = ("parity", "cpu_baseline", "host_enqueue_us_per_frame", "host_enqueue_frac", "synchronous_frame_path",
+                  "host_image_path", "pinned_h2d_path", "tsdf_system_path", "tsdf_only", "multi_stream", "secondary",
+                  "flythrough")
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_steps_and_leaves_every_other_leg_to_full():
+    """Without --full the run sets up, warms up, times the steps and prints the line: every other leg and check is
+    null, whatever their own options say (here their defaults).  With --full the same options bring them back."""
+    common = ["--steps", "2", "--warmup", "1", "--reps", "1", "--frames-per-step", "12"]
+    r = _run(common, {}, 600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["roofline"]["launches"] > 0          # measured inside the timed region: part of a plain run
+    assert {k: d[k] for k in FULL_ONLY_KEYS} == {k: None for k in FULL_ONLY_KEYS}
+
+    r = _run(common + ["--full", "--cpu-frames", "12", "--host-frames", "0", "--no-secondary", "--streams", "0"], {}, 600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["parity"]["frames"] == 12 and d["parity"]["max_abs_tsdf"] == 0.0
+    assert d["cpu_baseline"]["value"] > 0 and d["host_enqueue_us_per_frame"] > 0
+
+
+@pytest.mark.gpu
+def test_a_plain_flythrough_run_leaves_parity_and_event_passes_to_full():
+    """--config flythrough: a plain run times the graph passes alone; --full adds the oracle over the whole pass and
+    the per-frame event passes."""
+    r = _run(["--config", "flythrough", "--flythrough-frames", "8"], {}, 600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    f = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["flythrough"]
+    assert f["frames_per_s"] > 0 and f["parity"] is None and f["frame_period_us"] is None and f["k_integrate_us"] is None
+    r = _run(["--config", "flythrough", "--flythrough-frames", "8", "--full"], {}, 600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    f = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["flythrough"]
+    assert f["parity"]["frames"] == 8 and f["parity"]["max_abs_tsdf"] == 0.0
+    assert f["frame_period_us"]["p50"] > 0 and f["k_integrate_us"]["p50"] > 0
+
+
+def test_full_is_off_unless_given():
+    bench = _bench_module()
+    for config in bench.CONFIG_DEFAULTS:
+        assert not bench.parse(["--config", config]).full and bench.parse(["--config", config, "--full"]).full
 
 
 def test_options_given_are_taken_as_given_under_every_config():

@@ -27,15 +27,15 @@ bash tools/traffic.sh "--config bigmap" traffic_bigmap.json > gpurun_out/traffic
 bash tools/traffic_group.sh 4 > gpurun_out/traffic_grp.log 2>&1
 echo "traffic done"
 SQ_NSETS=3 SQ_BIGMAP=1 bash tools/sq.sh $TAG > gpurun_out/sq_r05.log 2>&1; echo "sq rc=$?"
-timeout -k 10 800 python bench.py > gpurun_out/bench_default.log 2> gpurun_out/bench_default.err && tail -1 gpurun_out/bench_default.log > $O/${TAG}_bench_line.json; echo "bench rc=$?"
-timeout -k 10 500 python bench.py --config hd2mm --host-frames 0 --streams 0 > gpurun_out/bench_hd2mm.log 2>&1 && tail -1 gpurun_out/bench_hd2mm.log > $O/${TAG}_bench_line_hd2mm.json
-timeout -k 10 500 python bench.py --config bigmap > gpurun_out/bench_bigmap.log 2>&1 && tail -1 gpurun_out/bench_bigmap.log > $O/${TAG}_bench_line_bigmap.json
-timeout -k 10 500 python bench.py --config flythrough --host-frames 0 --streams 0 > gpurun_out/bench_fly.log 2>&1 && tail -1 gpurun_out/bench_fly.log > $O/${TAG}_bench_line_flythrough_hd2mm.json
+timeout -k 10 800 python bench.py --full > $O/bench_default.log 2> $O/bench_default.err && tail -1 $O/bench_default.log > $O/${TAG}_bench_line.json; echo "bench rc=$?"
+timeout -k 10 500 python bench.py --full --config hd2mm --host-frames 0 --streams 0 > $O/bench_hd2mm.log 2>&1 && tail -1 $O/bench_hd2mm.log > $O/${TAG}_bench_line_hd2mm.json
+timeout -k 10 500 python bench.py --full --config bigmap > $O/bench_bigmap.log 2>&1 && tail -1 $O/bench_bigmap.log > $O/${TAG}_bench_line_bigmap.json
+timeout -k 10 500 python bench.py --full --config flythrough --host-frames 0 --streams 0 > $O/bench_fly.log 2>&1 && tail -1 $O/bench_fly.log > $O/${TAG}_bench_line_flythrough_hd2mm.json
 echo "bench lines done"
 # BASELINE config 4 through the plain entry: 2 subvolume ranks on the ONE device, gloo instead of RCCL (a rehearsal
 # of the data path -- frame broadcast inside the timed region --, not a scaling measurement)
-RATSDF_BENCH_DEVICE=0 RATSDF_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --shard --config hd2mm --steps 3 --warmup 1 --reps 3 > gpurun_out/bench_shard2.log 2>&1 && grep '^{' gpurun_out/bench_shard2.log | tail -1 > $O/${TAG}_bench_line_shard2_rehearsal_hd2mm.json
-RATSDF_BENCH_DEVICE=0 RATSDF_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --shard --steps 3 --warmup 1 --reps 3 > gpurun_out/bench_shard2v.log 2>&1 && grep '^{' gpurun_out/bench_shard2v.log | tail -1 > $O/${TAG}_bench_line_shard2_rehearsal_vga5mm.json
+RATSDF_BENCH_DEVICE=0 RATSDF_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --shard --full --config hd2mm --steps 3 --warmup 1 --reps 3 > $O/bench_shard2.log 2>&1 && grep '^{' $O/bench_shard2.log | tail -1 > $O/${TAG}_bench_line_shard2_rehearsal_hd2mm.json
+RATSDF_BENCH_DEVICE=0 RATSDF_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --shard --full --steps 3 --warmup 1 --reps 3 > $O/bench_shard2v.log 2>&1 && grep '^{' $O/bench_shard2v.log | tail -1 > $O/${TAG}_bench_line_shard2_rehearsal_vga5mm.json
 echo "shard rehearsal rc=$?"
 timeout -k 10 300 python tools/zero_waves.py > $O/${TAG}_zero_update_waves.txt 2> gpurun_out/zero_waves.err
 timeout -k 5 60 tools/probes/h2d_probe > $O/${TAG}_h2d_probe.txt 2>&1

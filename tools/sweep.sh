@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/sweep.sh "VAR=v1 VAR=v2 ..."  -> one short bench line per setting (GPU box)
 for kv in "$@"; do
-  out=$(env $kv timeout -k 10 200 python bench.py --steps 4 --warmup 2 --cpu-frames 0 2>/dev/null | tail -1)
+  out=$(env $kv timeout -k 10 200 python bench.py --full --steps 4 --warmup 2 --cpu-frames 0 2>/dev/null | tail -1)
   python3 - "$kv" "$out" <<'PY'
 import json,sys
 kv,out=sys.argv[1],sys.argv[2]
