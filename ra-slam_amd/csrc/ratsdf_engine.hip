@@ -20,6 +20,10 @@
 
 #include "kernels_frame.h"
 #include "kernels_mesh.h"
+#include "kernels_sample.h"
+#include "../../include/ratsdf_sample.h"
+
+static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
 
 using namespace ratsdf;
 
@@ -216,6 +220,8 @@ struct ratsdf_engine {
   ratsdf_frame_stats* d_stats = nullptr;
   uint8_t *d_render = nullptr, *h_render = nullptr;  // ray casting through the host entry points: output + page-locked copy
   size_t render_cap = 0;
+  uint8_t *d_sample = nullptr, *h_sample = nullptr;  // point sampling through the host entry point: records | points,
+  size_t sample_cap = 0;                              // device + page-locked copy; capacity in points
   uint32_t* d_occ = nullptr;  // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
   EngineDev* d_eng = nullptr;  // device copy of the engine record (device_types.h)
@@ -436,6 +442,10 @@ int ratsdf_engine::free_all() {
   if (h_render) (void)hipHostFree(h_render);
   d_render = h_render = nullptr;
   render_cap = 0;
+  if (d_sample) (void)hipFree(d_sample);
+  if (h_sample) (void)hipHostFree(h_sample);
+  d_sample = h_sample = nullptr;
+  sample_cap = 0;
   if (dl_dev) (void)hipFree(dl_dev);
   if (dl_host) (void)hipHostFree(dl_host);
   for (auto& ev : stage_ev)
@@ -2196,6 +2206,71 @@ int ratsdf_raycast_rows(ratsdf_engine* e, const ratsdf_intrinsics* K, int height
 int ratsdf_raycast(ratsdf_engine* e, const ratsdf_intrinsics* K, int height, int width,
                    const ratsdf_pose* T, float max_depth, uint8_t* rgba, uint8_t* normal) {
   return ratsdf_raycast_rows(e, K, height, width, T, max_depth, 0, height, rgba, normal);
+}
+
+// ---- point sampling (include/ratsdf_sample.h, kernels_sample.h) ---------------------------------
+constexpr size_t kSampleChunk = (size_t)1 << 21;  // points per staged pass of the host entry point (88 MiB of buffers)
+constexpr size_t kSampleRecord = 32, kSamplePoint = 12;
+
+// a sticky error some finished launch has already raised, without waiting for the stream (ratsdf_engine::sticky)
+static int sticky_raised(ratsdf_engine* e) {
+  return *(volatile uint32_t*)e->h_err != 0u ? e->sticky() : RATSDF_OK;
+}
+
+static int sample_launch(ratsdf_engine* e, const float* d_xyz, size_t n, void* d_out) {
+  hipLaunchKernelGGL(k_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->tab, e->pool, d_xyz,
+                     (int)n, e->vs, (uint4*)d_out);
+  HIPCHK(hipGetLastError());
+  return RATSDF_OK;
+}
+
+int ratsdf_sample_points_device(ratsdf_engine* e, const void* d_xyz, size_t n, void* d_out) {
+  DeviceGuard guard(e ? e->device : -1);
+  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  if (!e || (n > 0 && (!d_xyz || !d_out)) || n > (size_t)INT32_MAX || ((uintptr_t)d_out & 15u) ||
+      ((uintptr_t)d_xyz & 3u))
+    return RATSDF_ERR_BAD_ARGUMENT;
+  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
+  { const int st0 = sticky_raised(e); if (st0 != RATSDF_OK) return st0; }
+  if (n == 0) return RATSDF_OK;
+  return sample_launch(e, (const float*)d_xyz, n, d_out);
+}
+
+int ratsdf_sample_points(ratsdf_engine* e, const float* xyz, size_t n, ratsdf_sample* out) {
+  DeviceGuard guard(e ? e->device : -1);
+  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  if (!e || (n > 0 && (!xyz || !out)) || n > (size_t)INT32_MAX) return RATSDF_ERR_BAD_ARGUMENT;
+  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
+  if (n == 0) return e->sticky();
+  // points in and records out through buffers the engine keeps, grown on demand (as the ray cast's d_render /
+  // h_render); a failed grow leaves no capacity behind, so the next call tries again
+  const size_t chunk = std::min(n, kSampleChunk);
+  if (e->sample_cap < chunk) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->d_sample) (void)hipFree(e->d_sample);
+    if (e->h_sample) (void)hipHostFree(e->h_sample);
+    e->d_sample = e->h_sample = nullptr;
+    e->sample_cap = 0;
+    HIPCHK(hipMalloc(&e->d_sample, chunk * (kSampleRecord + kSamplePoint)));
+    HIPCHK(hipHostMalloc(&e->h_sample, chunk * (kSampleRecord + kSamplePoint), hipHostMallocDefault));
+    e->sample_cap = chunk;
+  }
+  const size_t cap = e->sample_cap;
+  uint8_t* d_rec = e->d_sample;
+  float* d_pts = (float*)(e->d_sample + cap * kSampleRecord);
+  uint8_t* h_rec = e->h_sample;
+  float* h_pts = (float*)(e->h_sample + cap * kSampleRecord);
+  for (size_t o = 0; o < n; o += chunk) {
+    const size_t m = std::min(chunk, n - o);
+    memcpy(h_pts, xyz + 3 * o, m * kSamplePoint);
+    HIPCHK(hipMemcpyAsync(d_pts, h_pts, m * kSamplePoint, hipMemcpyHostToDevice, e->stream));
+    const int st = sample_launch(e, d_pts, m, d_rec);
+    if (st != RATSDF_OK) return st;
+    HIPCHK(hipMemcpyAsync(h_rec, d_rec, m * kSampleRecord, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(out + o, h_rec, m * kSampleRecord);
+  }
+  return e->sticky();
 }
 
 // exclusive positions of the set items of a 0/1 mask; returns the number of set items

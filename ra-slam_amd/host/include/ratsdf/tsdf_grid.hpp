@@ -43,6 +43,8 @@ struct Api {
   int (*save_map)(ratsdf_engine*, const char*) = nullptr;
   int (*load_map)(ratsdf_engine*, const char*) = nullptr;
   int (*map_file_info)(const char*, ratsdf_config*, int64_t*) = nullptr;
+  // include/ratsdf_sample.h: likewise optional (not in the CPU oracle)
+  int (*sample_points)(ratsdf_engine*, const float*, size_t, ratsdf_sample*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -93,6 +95,10 @@ class TSDFGrid {
   // bit-exactly.  Return the status (also kept in last_status()); no reference counterpart.
   int SaveMap(const std::string& path);
   int LoadMap(const std::string& path);
+  // batched point sampling (include/ratsdf_sample.h): n world points (xyz: 3 floats each, metres) -> n records of the
+  // trilinear TSDF, its gradient, the nearest voxel's probability and colour.  Returns the status (also kept in
+  // last_status()); no reference counterpart (its nearest relative is RetrieveTSDF, with mirrored weights).
+  int SamplePoints(const float* xyz, size_t n, ratsdf_sample* out);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

@@ -146,6 +146,8 @@ class TSDFSystem {
   // map checkpoints (include/ratsdf_map.h): Flush() first, then under the engine's mutex; return the status
   int SaveMap(const std::string& path);
   int LoadMap(const std::string& path);
+  // TSDFGrid::SamplePoints under the engine's mutex, like Query: the map as integrated so far
+  int Sample(const float* xyz, size_t n, ratsdf_sample* out);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

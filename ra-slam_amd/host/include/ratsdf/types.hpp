@@ -14,6 +14,7 @@
 
 #include "../../../../include/ratsdf.h"
 #include "../../../../include/ratsdf_map.h"
+#include "../../../../include/ratsdf_sample.h"
 
 namespace ratsdf {
 

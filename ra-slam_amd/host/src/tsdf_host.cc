@@ -77,6 +77,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.save_map = reinterpret_cast<decltype(api.save_map)>(opt_sym("save_map"));
   api.load_map = reinterpret_cast<decltype(api.load_map)>(opt_sym("load_map"));
   api.map_file_info = reinterpret_cast<decltype(api.map_file_info)>(opt_sym("map_file_info"));
+  api.sample_points = reinterpret_cast<decltype(api.sample_points)>(opt_sym("sample_points"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -219,6 +220,12 @@ int TSDFGrid::SaveMap(const std::string& path) {
 int TSDFGrid::LoadMap(const std::string& path) {
   if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   note(api_->load_map ? api_->load_map(engine_, path.c_str()) : RATSDF_ERR_NOT_IMPLEMENTED, "LoadMap");
+  return status_;
+}
+
+int TSDFGrid::SamplePoints(const float* xyz, size_t n, ratsdf_sample* out) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->sample_points ? api_->sample_points(engine_, xyz, n, out) : RATSDF_ERR_NOT_IMPLEMENTED, "SamplePoints");
   return status_;
 }
 
@@ -479,6 +486,11 @@ int TSDFSystem::LoadMap(const std::string& path) {
   Flush();
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.LoadMap(path);
+}
+
+int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.SamplePoints(xyz, n, out);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

@@ -7,7 +7,7 @@ import os
 from pathlib import Path
 
 from . import _abi
-from ._abi import (BLOCK_DTYPE, RGBW_DTYPE, VOXEL_SEGM_DTYPE, VOXEL_TSDF_DTYPE, Bounds, Engine, Group,
+from ._abi import (BLOCK_DTYPE, RGBW_DTYPE, SAMPLE_DTYPE, VOXEL_SEGM_DTYPE, VOXEL_TSDF_DTYPE, Bounds, Engine, Group,
                    Intrinsics, Library, Pose, RatsdfError)
 from .pose import compose, identity_pose, invert, pose_from_matrix
 
@@ -45,4 +45,4 @@ class TSDFGrid(Engine):
 
 __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "Pose", "Bounds",
            "RatsdfError", "map_file_info", "pose_from_matrix", "compose", "invert", "identity_pose", "BLOCK_DTYPE",
-           "RGBW_DTYPE", "VOXEL_TSDF_DTYPE", "VOXEL_SEGM_DTYPE", "LIB_PATH"]
+           "RGBW_DTYPE", "SAMPLE_DTYPE", "VOXEL_TSDF_DTYPE", "VOXEL_SEGM_DTYPE", "LIB_PATH"]

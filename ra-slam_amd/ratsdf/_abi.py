@@ -82,6 +82,13 @@ SYMBOLS = [
 # include/ratsdf_map.h (map checkpoints): bound when the library has them -- the CPU oracle does not, and there the
 # methods raise RatsdfError with status 6 (not implemented)
 MAP_SYMBOLS = ["save_map", "load_map", "map_file_info"]
+# include/ratsdf_sample.h (batched point sampling): handled like MAP_SYMBOLS -- the oracle reports status 6
+SAMPLE_SYMBOLS = ["sample_points", "sample_points_device"]
+# ratsdf_sample (32 bytes); flags: SAMPLE_ALLOCATED | SAMPLE_OBSERVED | SAMPLE_NEAREST
+SAMPLE_DTYPE = np.dtype([("tsdf", "<f4"), ("grad", "<f4", (3,)), ("prob", "<f4"), ("rgbw", RGBW_DTYPE),
+                         ("min_weight", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
+SAMPLE_ALLOCATED, SAMPLE_OBSERVED, SAMPLE_NEAREST = 1, 2, 4
+assert SAMPLE_DTYPE.itemsize == 32
 
 
 class _OwnedBuffer:
@@ -196,6 +203,14 @@ class Library:
                 f.restype = C.c_int
                 f.argtypes = {"save_map": [vp, C.c_char_p], "load_map": [vp, C.c_char_p],
                               "map_file_info": [C.c_char_p, C.POINTER(Config), C.POINTER(C.c_int64)]}[s]
+            self.fn[s] = f
+        for s in SAMPLE_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = [vp, vp, C.c_size_t, vp]
             self.fn[s] = f
 
     def backend(self):
@@ -496,6 +511,25 @@ class Engine:
         _check(self.lib.fn["raycast_rows"](self._h, C.byref(k), height, width, C.byref(p), float(max_depth),
                                            int(row0), int(row1), rgba.ctypes.data, normal.ctypes.data), "raycast_rows")
         return rgba, normal
+
+    def sample_points(self, points):
+        """batched point sampling (ratsdf_sample_points, include/ratsdf_sample.h): points of shape (n, 3) in metres;
+        returns n SAMPLE_DTYPE records (trilinear tsdf, its gradient per metre, the nearest voxel's probability and
+        colour, the corners' smallest weight, flags)"""
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("points must have shape (n, 3)")
+        n = p.shape[0]
+        out = np.zeros(n, dtype=SAMPLE_DTYPE)
+        _check(self.lib.fn["sample_points"](self._h, p.ctypes.data if n else None, n, out.ctypes.data if n else None),
+               "sample_points")
+        return out
+
+    def sample_points_device(self, d_xyz, n, d_out):
+        """sample_points() on DEVICE buffers (n x 3 float32 in, n 32-byte records out, 16-byte aligned), asynchronous
+        on the engine's stream"""
+        _check(self.lib.fn["sample_points_device"](self._h, d_xyz or None, int(n), d_out or None),
+               "sample_points_device")
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,
