@@ -45,6 +45,8 @@ struct Api {
   int (*map_file_info)(const char*, ratsdf_config*, int64_t*) = nullptr;
   // include/ratsdf_sample.h: likewise optional (not in the CPU oracle)
   int (*sample_points)(ratsdf_engine*, const float*, size_t, ratsdf_sample*) = nullptr;
+  // include/ratsdf_esdf.h: likewise optional (not in the CPU oracle)
+  int (*esdf)(ratsdf_engine*, const int32_t*, const int32_t*, float, uint32_t, float*, uint8_t*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -99,6 +101,11 @@ class TSDFGrid {
   // trilinear TSDF, its gradient, the nearest voxel's probability and colour.  Returns the status (also kept in
   // last_status()); no reference counterpart (its nearest relative is RetrieveTSDF, with mirrored weights).
   int SamplePoints(const float* xyz, size_t n, ratsdf_sample* out);
+  // Euclidean signed distance field over a box of voxels (include/ratsdf_esdf.h): origin / dims in voxel indices,
+  // out: dims[0]*dims[1]*dims[2] floats (metres, x fastest), state: as many bytes or nullptr.  Returns the status
+  // (also kept in last_status()); no reference counterpart.
+  int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
+           uint8_t* state = nullptr);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

@@ -148,6 +148,9 @@ class TSDFSystem {
   int LoadMap(const std::string& path);
   // TSDFGrid::SamplePoints under the engine's mutex, like Query: the map as integrated so far
   int Sample(const float* xyz, size_t n, ratsdf_sample* out);
+  // TSDFGrid::ESDF under the engine's mutex, like Sample
+  int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
+           uint8_t* state = nullptr);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

@@ -78,6 +78,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.load_map = reinterpret_cast<decltype(api.load_map)>(opt_sym("load_map"));
   api.map_file_info = reinterpret_cast<decltype(api.map_file_info)>(opt_sym("map_file_info"));
   api.sample_points = reinterpret_cast<decltype(api.sample_points)>(opt_sym("sample_points"));
+  api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -226,6 +227,14 @@ int TSDFGrid::LoadMap(const std::string& path) {
 int TSDFGrid::SamplePoints(const float* xyz, size_t n, ratsdf_sample* out) {
   if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   note(api_->sample_points ? api_->sample_points(engine_, xyz, n, out) : RATSDF_ERR_NOT_IMPLEMENTED, "SamplePoints");
+  return status_;
+}
+
+int TSDFGrid::ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
+                   uint8_t* state) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->esdf ? api_->esdf(engine_, origin, dims, occupied_below, flags, out, state) : RATSDF_ERR_NOT_IMPLEMENTED,
+       "ESDF");
   return status_;
 }
 
@@ -491,6 +500,12 @@ int TSDFSystem::LoadMap(const std::string& path) {
 int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.SamplePoints(xyz, n, out);
+}
+
+int TSDFSystem::ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
+                     uint8_t* state) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.ESDF(origin, dims, occupied_below, flags, out, state);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

@@ -89,6 +89,10 @@ SAMPLE_DTYPE = np.dtype([("tsdf", "<f4"), ("grad", "<f4", (3,)), ("prob", "<f4")
                          ("min_weight", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
 SAMPLE_ALLOCATED, SAMPLE_OBSERVED, SAMPLE_NEAREST = 1, 2, 4
 assert SAMPLE_DTYPE.itemsize == 32
+# include/ratsdf_esdf.h (Euclidean signed distance field over a box): handled like SAMPLE_SYMBOLS
+ESDF_SYMBOLS = ["esdf", "esdf_device"]
+ESDF_UNKNOWN_OCCUPIED = 1
+ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
 
 
 class _OwnedBuffer:
@@ -212,6 +216,14 @@ class Library:
                 f.restype = C.c_int
                 f.argtypes = [vp, vp, C.c_size_t, vp]
             self.fn[s] = f
+        for s in ESDF_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_uint32, vp, vp]
+            self.fn[s] = f
 
     def backend(self):
         return self.fn["backend"]().decode()
@@ -228,6 +240,39 @@ class Library:
 def _check(st, what):
     if st != 0:
         raise RatsdfError(st, what)
+
+
+def _box3(v, what):
+    """three int32 of a voxel box (origin or dims) for the ESDF entry points"""
+    a = np.asarray(v).reshape(-1)
+    if a.shape != (3,) or not np.all(a == np.trunc(a.astype(np.float64))):
+        raise ValueError(f"{what} must be three integers")
+    if np.any(a < -(1 << 31)) or np.any(a >= (1 << 31)):
+        raise ValueError(f"{what} out of the int32 range")
+    return (C.c_int32 * 3)(*(int(x) for x in a))
+
+
+def _esdf_flags(unknown_occupied):
+    """the flags word: a bool, or the raw word itself (an int: unknown bits reach the library, which refuses them)"""
+    if isinstance(unknown_occupied, (bool, np.bool_)):
+        return C.c_uint32(ESDF_UNKNOWN_OCCUPIED if unknown_occupied else 0)
+    return C.c_uint32(int(unknown_occupied))
+
+
+def voxel_box(lo, hi, voxel_size):
+    """(origin, dims) of the voxel box that covers the metric box [lo, hi] (3 floats each, metres): per axis the
+    voxel indices floor(float32(lo / vs)) .. floor(float32(hi / vs)), both ends inclusive, the quotient evaluated in
+    float32 as the engine's kernels do.  Raises ValueError for a non-finite corner or hi below lo."""
+    vs = np.float32(voxel_size)
+    lo = np.asarray(lo, dtype=np.float32).reshape(3)
+    hi = np.asarray(hi, dtype=np.float32).reshape(3)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("box corners must be finite")
+    a = np.floor(lo / vs).astype(np.int64)
+    b = np.floor(hi / vs).astype(np.int64)
+    if np.any(b < a):
+        raise ValueError("hi must not lie below lo")
+    return [int(v) for v in a], [int(v) for v in b - a + 1]
 
 
 def _as_pose(pose):
@@ -530,6 +575,29 @@ class Engine:
         on the engine's stream"""
         _check(self.lib.fn["sample_points_device"](self._h, d_xyz or None, int(n), d_out or None),
                "sample_points_device")
+
+    def esdf(self, origin, dims, occupied_below=0.0, unknown_occupied=False, with_state=False):
+        """Euclidean signed distance field over a box of voxels (ratsdf_esdf, include/ratsdf_esdf.h): origin is the
+        voxel index of the box's minimum corner, dims the voxels per axis (x, y, z).  Returns a float32 array of shape
+        (dims[2], dims[1], dims[0]) -- metres to the nearest obstacle voxel, negative inside obstacles -- and, with
+        with_state, the uint8 ESDF_STATE_* of every voxel as a second array of the same shape."""
+        o, d = _box3(origin, "origin"), _box3(dims, "dims")
+        n = int(np.prod([int(v) for v in d], dtype=object))
+        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
+        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+        out = np.empty(shape, dtype=np.float32)
+        state = np.empty(shape, dtype=np.uint8) if with_state else None
+        _check(self.lib.fn["esdf"](self._h, o, d, C.c_float(occupied_below), _esdf_flags(unknown_occupied),
+                                   out.ctypes.data, state.ctypes.data if with_state else None), "esdf")
+        return (out, state) if with_state else out
+
+    def esdf_device(self, origin, dims, d_out, d_state=0, occupied_below=0.0, unknown_occupied=False):
+        """esdf() into DEVICE buffers (d_out: dims[0]*dims[1]*dims[2] float32, 16-byte aligned; d_state: as many
+        bytes, or 0 for none), asynchronous on the engine's stream.  Raw pointers: torch data_ptr() or
+        devmem.DeviceArray.data_ptr()."""
+        _check(self.lib.fn["esdf_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
+                                          C.c_float(occupied_below), _esdf_flags(unknown_occupied), d_out or None,
+                                          d_state or None), "esdf_device")
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,
