@@ -145,30 +145,30 @@ struct FileCloser {
 
 // Page-locked double buffers and device staging for the voxel records of a save or a load.
 struct MapStaging {
-  uint8_t* host[2] = {nullptr, nullptr};
+  HostMem host_mem[2];
+  DevMem dev_mem[2], idx_mem;
+  uint8_t* host[2] = {nullptr, nullptr};  // (views of the above)
   uint8_t* dev[2] = {nullptr, nullptr};
   int32_t* d_idx = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  ~MapStaging() {
-    for (int i = 0; i < 2; ++i) {
+  ~MapStaging() {  // (the copies the events stand for have finished before the members free their memory)
+    for (int i = 0; i < 2; ++i)
       if (ev[i]) (void)hipEventSynchronize(ev[i]), (void)hipEventDestroy(ev[i]);
-      if (host[i]) (void)hipHostFree(host[i]);
-      if (dev[i]) (void)hipFree(dev[i]);
-    }
-    if (d_idx) (void)hipFree(d_idx);
   }
-  hipError_t init(const std::vector<int32_t>& idx, hipStream_t s) {
+  int init(const std::vector<int32_t>& idx, hipStream_t s) {
     const size_t bytes = (size_t)kMapChunk * kMapRecordBytes;
-    hipError_t r = hipSuccess;
-    for (int i = 0; i < 2 && r == hipSuccess; ++i) {
-      r = hipHostMalloc(&host[i], bytes, hipHostMallocDefault);
-      if (r == hipSuccess) r = hipMalloc(&dev[i], bytes);
-      if (r == hipSuccess) r = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+    for (int i = 0; i < 2; ++i) {
+      STCHK(host_mem[i].alloc(bytes));
+      STCHK(dev_mem[i].alloc(bytes));
+      HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+      host[i] = host_mem[i].as<uint8_t>();
+      dev[i] = dev_mem[i].as<uint8_t>();
     }
-    if (r == hipSuccess) r = hipMalloc(&d_idx, std::max<size_t>(idx.size(), 1) * 4);
-    if (r == hipSuccess && !idx.empty()) r = hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s);
-    if (r == hipSuccess) r = hipStreamSynchronize(s);
-    return r;
+    STCHK(idx_mem.alloc(std::max<size_t>(idx.size(), 1) * 4));
+    d_idx = idx_mem.as<int32_t>();
+    if (!idx.empty()) HIPCHK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RATSDF_OK;
   }
 };
 
@@ -390,7 +390,7 @@ int ratsdf_save_map(ratsdf_engine* e, const char* path) {
   const std::vector<MapChunk> chunks = map_chunks(h.n_blocks, (uint32_t)(pool_idx.size() - h.n_blocks));
   if (ok && !chunks.empty()) {
     MapStaging sg;
-    if (sg.init(pool_idx, e->stream) != hipSuccess) {
+    if (sg.init(pool_idx, e->stream) != RATSDF_OK) {
       dev_st = RATSDF_ERR_DEVICE;
     } else {
       auto enqueue = [&](size_t k) -> bool {
@@ -453,14 +453,15 @@ int ratsdf_load_map(ratsdf_engine* e, const char* path) {
   Table& t = e->tab;
   int st = RATSDF_OK;
   MapStaging sg;
-  uint4* d_entries = nullptr;
+  DevMem entries_mem;
   do {
-    if (sg.init(m.pool_idx, e->stream) != hipSuccess) { st = RATSDF_ERR_DEVICE; break; }
+    if (sg.init(m.pool_idx, e->stream) != RATSDF_OK) { st = RATSDF_ERR_DEVICE; break; }
     hipLaunchKernelGGL(k_init_table, dim3((t.num_entry + 255) / 256), dim3(256), 0, e->stream, t.entries, t.claim,
                        t.occ, t.num_entry, t.num_bucket);
     if (!m.entries.empty()) {
-      if (hipMalloc(&d_entries, m.entries.size() * sizeof(MapEntry)) != hipSuccess ||
-          hipMemcpyAsync(d_entries, m.entries.data(), m.entries.size() * sizeof(MapEntry), hipMemcpyHostToDevice,
+      if (entries_mem.alloc(m.entries.size() * sizeof(MapEntry)) != RATSDF_OK) { st = RATSDF_ERR_DEVICE; break; }
+      uint4* d_entries = entries_mem.as<uint4>();
+      if (hipMemcpyAsync(d_entries, m.entries.data(), m.entries.size() * sizeof(MapEntry), hipMemcpyHostToDevice,
                          e->stream) != hipSuccess) { st = RATSDF_ERR_DEVICE; break; }
       hipLaunchKernelGGL(k_map_scatter_entries, dim3((unsigned)((m.entries.size() + 255) / 256)), dim3(256), 0,
                          e->stream, t, d_entries, (uint32_t)m.entries.size());
@@ -504,9 +505,9 @@ int ratsdf_load_map(ratsdf_engine* e, const char* path) {
     // occupancy bits, Table::active, claims, counters, the delta log's overflow mark, the error: as ratsdf_recover
     st = rebuild_derived(e, true);
   } while (false);
-  if (d_entries) {
+  if (entries_mem) {
     (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(d_entries);
+    entries_mem.reset();
   }
   if (st != RATSDF_OK) {
     (void)hipStreamSynchronize(e->stream);

@@ -22,6 +22,7 @@
 #include "kernels_mesh.h"
 #include "kernels_sample.h"
 #include "kernels_esdf.h"
+#include "hip_mem.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
 
@@ -38,6 +39,8 @@ using namespace ratsdf;
       return RATSDF_ERR_DEVICE;                                                           \
     }                                                                                     \
   } while (0)
+// ... and a call that reports a RATSDF_* status of its own (an allocation through hip_mem.h's owners above all)
+#define STCHK(expr) do { const int st__ = (expr); if (st__ != RATSDF_OK) return st__; } while (0)
 
 // Scoped "current device" of the calling thread: HIP's current device is per thread and defaults to
 // 0, so every entry point that allocates or launches selects the engine's device first and restores
@@ -204,7 +207,37 @@ class HostCopyPool {
   bool stop_ = false;
 };
 
-struct ratsdf_engine {
+// What the engine owns of device and page-locked host memory: every buffer has ONE owner (hip_mem.h), and free_all()
+// drops them all by assigning an empty EngineMem.  `fixed` owns what is allocated once, at creation, pix_mem / rank_mem
+// the image-sized buffers (ensure_image): the typed pointers in Table, Pool and the engine's fields are views of them
+// (those structures go to the kernels by value).  A buffer that grows on demand is its own owner; a capacity counted
+// in other units than bytes (pixels, voxels) is zero while its buffers are replaced, so a failed grow is retried.
+struct EngineMem {
+  std::vector<DevMem> fixed, pix_mem, rank_mem;
+  HostMem h_err_page;  // (ratsdf_engine::h_err)
+  DevMem d_render;     // ray casting through the host entry points: output, and its page-locked copy
+  HostMem h_render;
+  DevMem d_sample;     // point sampling through the host entry point: records | points, and the page-locked copy
+  HostMem h_sample;
+  DevMem d_esdf;       // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks (ratsdf_engine::esdf_cap)
+  HostMem h_esdf;      // page-locked copy of the host entry point's results, passed through in chunks
+  DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
+  DevMem d_mc;         // marching-cubes tables, built on first use
+  DevMem dl_dev;       // query-side downloads (grow-only)
+  HostMem dl_host;
+  HostMem h_stage;     // staging ring of the host-image entry points (ratsdf_engine::stage_pix)
+  DevMem d_stage;
+
+  template <class T>
+  static int own(std::vector<DevMem>& set, T** view, size_t bytes) {
+    set.emplace_back();
+    const int st = set.back().alloc(bytes);
+    *view = set.back().as<T>();  // (null after a failure)
+    return st;
+  }
+};
+
+struct ratsdf_engine : EngineMem {
   int device = 0;
   hipStream_t stream = nullptr;
   float vs = 0, trunc = 0;
@@ -220,15 +253,8 @@ struct ratsdf_engine {
   Pool pool{};
   Ctl* ctl = nullptr;
   ratsdf_frame_stats* d_stats = nullptr;
-  uint8_t *d_render = nullptr, *h_render = nullptr;  // ray casting through the host entry points: output + page-locked copy
-  size_t render_cap = 0;
-  uint8_t *d_sample = nullptr, *h_sample = nullptr;  // point sampling through the host entry point: records | points,
-  size_t sample_cap = 0;                              // device + page-locked copy; capacity in points
-  uint8_t* d_esdf = nullptr;  // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks; capacity in voxels
-  size_t esdf_cap = 0;
-  uint8_t* h_esdf = nullptr;  // page-locked copy of the host entry point's results, passed through in chunks
-  size_t h_esdf_cap = 0;      // bytes
-  uint32_t* d_occ = nullptr;  // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
+  int grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes);
+  size_t esdf_cap = 0;        // voxels the ESDF workspace was laid out for
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
   EngineDev* d_eng = nullptr;  // device copy of the engine record (device_types.h)
 
@@ -308,21 +334,14 @@ struct ratsdf_engine {
   uint32_t* dbitmap = nullptr;   // delete bitmap indexed by hash entry (self-cleaning)
   uint32_t* dsummary = nullptr;
   uint32_t* dprefix = nullptr;
-  void* d_mc = nullptr;   // marching-cubes tables (device), built on first use
   uint32_t vis_cap = 0;   // total items of `vis`
   uint32_t seg_cap = 0;   // items per work list (vis holds kNumLists + 1 segments)
   uint32_t dwords = 0;
   SlowDelete* slowdel[2] = {nullptr, nullptr};
 
-  // query-side download buffers (grow-only)
-  void* dl_dev = nullptr;
-  void* dl_host = nullptr;
-  size_t dl_cap = 0;
 
   // staging for the host-image entry points: kStageSlots frames of 16 bytes/pixel each
   size_t stage_pix = 0;
-  uint8_t* h_stage = nullptr;  // pinned
-  uint8_t* d_stage = nullptr;
   hipEvent_t stage_ev[kStageSlots] = {};  // upload of the slot's last user has been executed
   hipEvent_t use_ev[kStageSlots + 1] = {};  // the frame that read the slot has been executed (+1: call fence)
   hipStream_t copy_stream = nullptr;   // uploads of ratsdf_integrate_batch: even frames
@@ -334,7 +353,11 @@ struct ratsdf_engine {
   // a frame with ht / lt has been integrated, or blocks were imported with their probabilities (FrameParams::segm_live)
   mutable bool ever_sem = false;
   bool sync_integrate = false;         // RATSDF_SYNC_INTEGRATE=1: wait for every frame (the round-3 behaviour)
-  HostCopyPool* copy_pool = nullptr;
+  HostCopyPool* copy_pool = nullptr;   // started on first use: host_copy_pool()
+  HostCopyPool* host_copy_pool() {     // (nullptr when it cannot be had: the callers copy by themselves then)
+    if (!copy_pool) copy_pool = new (std::nothrow) HostCopyPool(3);
+    return copy_pool;
+  }
 
   // HIP graphs of the batch entry point (ratsdf_integrate_device_batch): the launches of an n-frame batch are
   // captured once per (image size, n) -- the kernels of the group path with one member, which take every
@@ -344,8 +367,8 @@ struct ratsdf_engine {
     int H = 0, W = 0, n = 0;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    FrameJob* d_jobs = nullptr;
-    FrameJob* h_jobs[2] = {nullptr, nullptr};  // page-locked, used alternately
+    DevMem d_jobs;      // FrameJob[n]
+    HostMem h_jobs[2];  // page-locked, used alternately
     hipEvent_t ev[2] = {nullptr, nullptr};     // the copy out of h_jobs[i] has been executed
     unsigned turn = 0;
     uint64_t last_use = 0;
@@ -426,12 +449,6 @@ FrameParams ratsdf_engine::base_params() const {
 
 int ratsdf_engine::free_all() {
   if (stream) (void)hipStreamSynchronize(stream);
-  void* ptrs[] = {tab.active, tab.del_log, tab.del_count, tab.entries, tab.claim, tab.occ, pool.rgbw, pool.tsdf, pool.segm, pool.heap, ctl,
-                  d_stats, d_eng, texA[0], texA[1], texB[0], texB[1], cand[0].list, cand[1].list, cand_count,
-                  req, req_k, win_ranks, abitmap, asummary, aprefix,
-                  slow, xlocks,
-                  sort_scratch, masks, wg_count, vis, del_list[0], del_list[1], upd_wg[0],
-                  upd_wg[1], tab.dclaim, dbitmap, dsummary, dprefix, slowdel[0], slowdel[1], d_stage, d_mc, serial_scratch, d_occ};
   if (copy_stream) (void)hipStreamSynchronize(copy_stream);
   if (copy_stream2) (void)hipStreamSynchronize(copy_stream2);
   if (stream) (void)hipStreamSynchronize(stream);
@@ -439,25 +456,8 @@ int ratsdf_engine::free_all() {
   copy_pool = nullptr;
   for (auto& g : graphs) free_graph(g);
   graphs.clear();
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (h_stage) (void)hipHostFree(h_stage);
-  if (h_err) (void)hipHostFree(h_err);
-  h_err = nullptr;
-  if (d_render) (void)hipFree(d_render);
-  if (h_render) (void)hipHostFree(h_render);
-  d_render = h_render = nullptr;
-  render_cap = 0;
-  if (d_sample) (void)hipFree(d_sample);
-  if (h_sample) (void)hipHostFree(h_sample);
-  d_sample = h_sample = nullptr;
-  sample_cap = 0;
-  if (d_esdf) (void)hipFree(d_esdf);
-  if (h_esdf) (void)hipHostFree(h_esdf);
-  d_esdf = h_esdf = nullptr;
-  esdf_cap = h_esdf_cap = 0;
-  if (dl_dev) (void)hipFree(dl_dev);
-  if (dl_host) (void)hipHostFree(dl_host);
+  // memory: the views in tab / pool and the engine's raw pointers dangle from here on (the engine is deleted next)
+  static_cast<EngineMem&>(*this) = EngineMem();
   for (auto& ev : stage_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : use_ev)
@@ -524,40 +524,40 @@ int ratsdf_engine::upload_record() {
 int ratsdf_engine::ensure_image(size_t npix, size_t nranks) {
   if (npix <= pix_cap && nranks == cur_nranks) return RATSDF_OK;
   HIPCHK(hipStreamSynchronize(stream));
+  // What describes a set of buffers (capacity, the sizes the kernels are given, the views) is cleared before the set is
+  // replaced and written once ALL of it exists: after a failure the next call comes through here again.
   if (npix > pix_cap) {
+    pix_cap = 0;
+    pix_mem.clear();
+    texA[0] = texA[1] = nullptr;
+    texB[0] = texB[1] = nullptr;
     for (int i = 0; i < 2; ++i) {
-      if (texA[i]) (void)hipFree(texA[i]);
-      if (texB[i]) (void)hipFree(texB[i]);
-      texA[i] = nullptr;
-      texB[i] = nullptr;
-      HIPCHK(hipMalloc(&texA[i], npix * sizeof(float4)));
-      HIPCHK(hipMalloc(&texB[i], npix * sizeof(uint32_t)));
+      STCHK(own(pix_mem, &texA[i], npix * sizeof(float4)));
+      STCHK(own(pix_mem, &texB[i], npix * sizeof(uint32_t)));
     }
     pix_cap = npix;
   }
   if (nranks > rank_cap) {
+    rank_cap = cur_nranks = 0;
+    req_cap = awords_cap = asum_words = cand[0].seg_cap = cand[1].seg_cap = 0;
+    rank_mem.clear();
+    req = nullptr;
+    req_k = abitmap = asummary = aprefix = nullptr;
+    cand[0].list = cand[1].list = nullptr;
     // candidate lists: every sample of the image could in principle ask for a different block
     const uint32_t seg = (uint32_t)((nranks + kCandSegs - 1) / kCandSegs) + 1024;
-    for (int i = 0; i < 2; ++i) {
-      if (cand[i].list) (void)hipFree(cand[i].list);
-      cand[i].list = nullptr;
-      HIPCHK(hipMalloc(&cand[i].list, (size_t)seg * kCandSegs * sizeof(uint4)));
-      cand[i].seg_cap = seg;
-    }
-    if (req) (void)hipFree(req);
-    if (req_k) (void)hipFree(req_k);
-    if (abitmap) (void)hipFree(abitmap);
-    if (asummary) (void)hipFree(asummary);
-    if (aprefix) (void)hipFree(aprefix);
+    const uint32_t words = ((uint32_t)((nranks + 31) / 32) + kGroupWords - 1) / kGroupWords * kGroupWords;
+    const uint32_t sum_words = (words / kGroupWords + 31) / 32;
+    for (int i = 0; i < 2; ++i) STCHK(own(rank_mem, &cand[i].list, (size_t)seg * kCandSegs * sizeof(uint4)));
+    STCHK(own(rank_mem, &req, (size_t)(uint32_t)nranks * sizeof(Request)));
+    STCHK(own(rank_mem, &req_k, (size_t)(uint32_t)nranks * 4));
+    STCHK(own(rank_mem, &abitmap, (size_t)words * 4));
+    STCHK(own(rank_mem, &asummary, (size_t)sum_words * 4));
+    STCHK(own(rank_mem, &aprefix, (size_t)words * 4));
+    cand[0].seg_cap = cand[1].seg_cap = seg;
     req_cap = (uint32_t)nranks;
-    awords_cap = (uint32_t)((nranks + 31) / 32);
-    awords_cap = (awords_cap + kGroupWords - 1) / kGroupWords * kGroupWords;
-    asum_words = (awords_cap / kGroupWords + 31) / 32;
-    HIPCHK(hipMalloc(&req, (size_t)req_cap * sizeof(Request)));
-    HIPCHK(hipMalloc(&req_k, (size_t)req_cap * 4));
-    HIPCHK(hipMalloc(&abitmap, (size_t)awords_cap * 4));
-    HIPCHK(hipMalloc(&asummary, (size_t)asum_words * 4));
-    HIPCHK(hipMalloc(&aprefix, (size_t)awords_cap * 4));
+    awords_cap = words;
+    asum_words = sum_words;
     rank_cap = nranks;
   }
   // the rank bitmap cleans itself after every use; start from a clean one when (re)allocated
@@ -574,13 +574,12 @@ int ratsdf_engine::ensure_stage(size_t npix) {
   if (copy_stream) HIPCHK(hipStreamSynchronize(copy_stream));
   if (copy_stream2) HIPCHK(hipStreamSynchronize(copy_stream2));
   HIPCHK(hipStreamSynchronize(stream));
-  if (h_stage) (void)hipHostFree(h_stage);
-  if (d_stage) (void)hipFree(d_stage);
-  h_stage = nullptr;
-  d_stage = nullptr;
+  stage_pix = 0;  // (a failure below leaves no capacity: the next call comes through here again)
   const size_t bytes = npix * 16 * kStageSlots;  // per slot: depth 4 + ht 4 + lt 4 + rgb 3 (padded to 4)
-  HIPCHK(hipHostMalloc(&h_stage, bytes, hipHostMallocDefault));
-  HIPCHK(hipMalloc(&d_stage, bytes));
+  h_stage.reset();
+  d_stage.reset();
+  STCHK(h_stage.alloc(bytes));
+  STCHK(d_stage.alloc(bytes));
   for (int i = 0; i < kStageSlots; ++i)
     if (!stage_ev[i]) HIPCHK(hipEventCreateWithFlags(&stage_ev[i], hipEventDisableTiming));
   for (int i = 0; i <= kStageSlots; ++i)
@@ -589,6 +588,17 @@ int ratsdf_engine::ensure_stage(size_t npix) {
   if (!copy_stream2) HIPCHK(hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking));
   stage_pix = npix;
   return RATSDF_OK;
+}
+
+// A device buffer and its page-locked twin, regrown together (to `bytes`) when either holds less than `need`; the
+// stream is drained first: what it has queued may still use the old ones.
+int ratsdf_engine::grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes) {
+  if (need <= d.size() && need <= h.size()) return RATSDF_OK;
+  HIPCHK(hipStreamSynchronize(stream));
+  d.reset();
+  h.reset();
+  STCHK(d.alloc(bytes));
+  return h.alloc(bytes);
 }
 
 // rank kernel (resolve + mark + scan) on a rank space of `nranks`; the commit itself happens inside
@@ -982,12 +992,9 @@ static bool finite_frame(const ratsdf_intrinsics& K, const ratsdf_pose& T, float
 void ratsdf_engine::free_graph(BatchGraph& g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (g.graph) (void)hipGraphDestroy(g.graph);
-  if (g.d_jobs) (void)hipFree(g.d_jobs);
-  for (int i = 0; i < 2; ++i) {
-    if (g.h_jobs[i]) (void)hipHostFree(g.h_jobs[i]);
+  for (int i = 0; i < 2; ++i)
     if (g.ev[i]) (void)hipEventDestroy(g.ev[i]);
-  }
-  g = BatchGraph();
+  g = BatchGraph();  // (and with it the job tables)
 }
 
 // The graph of an n-frame batch at H x W (built on first use, a few kept): k_cand_g for the first frame, then
@@ -1025,9 +1032,10 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
     graph_failed.push_back(GraphShape{H, W, n});
     return RATSDF_ERR_DEVICE;
   };
-  if (hipMalloc(&g.d_jobs, (size_t)n * sizeof(FrameJob)) != hipSuccess) return fail("hipMalloc");
+  if (g.d_jobs.alloc((size_t)n * sizeof(FrameJob)) != RATSDF_OK) return fail("hipMalloc");
+  FrameJob* const d_jobs = g.d_jobs.as<FrameJob>();
   for (int i = 0; i < 2; ++i)
-    if (hipHostMalloc(&g.h_jobs[i], (size_t)n * sizeof(FrameJob), hipHostMallocDefault) != hipSuccess ||
+    if (g.h_jobs[i].alloc((size_t)n * sizeof(FrameJob)) != RATSDF_OK ||
         hipEventCreateWithFlags(&g.ev[i], hipEventDisableTiming) != hipSuccess)
       return fail("staging allocation");
   const size_t npix = (size_t)H * W;
@@ -1043,13 +1051,13 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
     AheadGeom all = g0.a;
     all.first_tile = 0;
     all.n_tiles = g0.n_cand_wg * 4;
-    hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, 1), dim3(256), 0, stream, engs, (JobPtr)g.d_jobs, all);
+    hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, 1), dim3(256), 0, stream, engs, (JobPtr)d_jobs, all);
   }
   for (int f = 0; f < n; ++f) {
     const bool has_next = f + 1 < n;
     const Geom& gg = has_next ? g1 : g0;
-    JobPtr cur = (JobPtr)(g.d_jobs + f);
-    JobPtr nxt = (JobPtr)(g.d_jobs + (has_next ? f + 1 : f));
+    JobPtr cur = (JobPtr)(d_jobs + f);
+    JobPtr nxt = (JobPtr)(d_jobs + (has_next ? f + 1 : f));
 #ifdef RATSDF_STAMPS
     if (tab.tail_on)
       hipLaunchKernelGGL(k_front_g<true>, dim3(gg.n_front_wg, 1), dim3(256), 0, stream, engs, cur, nxt,
@@ -1080,7 +1088,7 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
     return fail("capture");
   if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) return fail("hipGraphInstantiate");
   g.last_use = ++graph_clock;
-  graphs.push_back(g);
+  graphs.push_back(std::move(g));
   *out = &graphs.back();
   return RATSDF_OK;
 }
@@ -1187,53 +1195,54 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   } while (0)
 
   CREATE_CHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CREATE_CHK(hipMalloc(&t.entries, (size_t)t.num_entry * sizeof(Entry)));
-  CREATE_CHK(hipMalloc(&t.claim, (size_t)t.num_bucket * 4));
+  CREATE_CHK(e->own(e->fixed, &t.entries, (size_t)t.num_entry * sizeof(Entry)));
+  CREATE_CHK(e->own(e->fixed, &t.claim, (size_t)t.num_bucket * 4));
   // occupancy bitmap, and behind it the dirty bitmap of the directory delta (device_types.h: Table)
-  CREATE_CHK(hipMalloc(&t.occ, (size_t)occ_words * 8 * 2));
+  CREATE_CHK(e->own(e->fixed, &t.occ, (size_t)occ_words * 8 * 2));
   CREATE_CHK(hipMemsetAsync(t.occ + occ_words, 0, (size_t)occ_words * 8, e->stream));
   // the live blocks by pool index (device_types.h: Table::active): every slot empty (idx = -1)
-  CREATE_CHK(hipMalloc(&t.active, (size_t)t.num_block * sizeof(VisItem)));
+  CREATE_CHK(e->own(e->fixed, &t.active, (size_t)t.num_block * sizeof(VisItem)));
   CREATE_CHK(hipMemsetAsync(t.active, 0xFF, (size_t)t.num_block * sizeof(VisItem), e->stream));
   t.del_cap = (uint32_t)t.num_block;
-  CREATE_CHK(hipMalloc(&t.del_log, (size_t)t.del_cap * sizeof(uint2)));
-  CREATE_CHK(hipMalloc(&t.del_count, 128));
+  CREATE_CHK(e->own(e->fixed, &t.del_log, (size_t)t.del_cap * sizeof(uint2)));
+  CREATE_CHK(e->own(e->fixed, &t.del_count, 128));
   CREATE_CHK(hipMemsetAsync(t.del_count, 0, 128, e->stream));
-  CREATE_CHK(hipMalloc(&e->pool.rgbw, nvox * 4));
-  CREATE_CHK(hipMalloc(&e->pool.tsdf, nvox * 4));
-  CREATE_CHK(hipMalloc(&e->pool.segm, nvox * 4));
-  CREATE_CHK(hipMalloc(&e->pool.heap, (size_t)t.num_block * 4));
-  CREATE_CHK(hipMalloc(&e->ctl, sizeof(Ctl)));
-  CREATE_CHK(hipMalloc(&e->d_stats, sizeof(ratsdf_frame_stats)));
-  CREATE_CHK(hipHostMalloc(&e->h_err, 512, hipHostMallocDefault));
-  CREATE_CHK(hipMalloc(&e->d_eng, sizeof(EngineDev)));
-  CREATE_CHK(hipMalloc(&e->slow, (size_t)kSlowCap * sizeof(SlowRequest)));
-  CREATE_CHK(hipMalloc(&e->xlocks, (size_t)kXLockCap * sizeof(XLock)));
-  CREATE_CHK(hipMalloc(&e->sort_scratch, (size_t)kSlowSortCap * sizeof(unsigned long long) +
+  CREATE_CHK(e->own(e->fixed, &e->pool.rgbw, nvox * 4));
+  CREATE_CHK(e->own(e->fixed, &e->pool.tsdf, nvox * 4));
+  CREATE_CHK(e->own(e->fixed, &e->pool.segm, nvox * 4));
+  CREATE_CHK(e->own(e->fixed, &e->pool.heap, (size_t)t.num_block * 4));
+  CREATE_CHK(e->own(e->fixed, &e->ctl, sizeof(Ctl)));
+  CREATE_CHK(e->own(e->fixed, &e->d_stats, sizeof(ratsdf_frame_stats)));
+  CREATE_CHK(e->h_err_page.alloc(512));
+  e->h_err = e->h_err_page.as<uint32_t>();
+  CREATE_CHK(e->own(e->fixed, &e->d_eng, sizeof(EngineDev)));
+  CREATE_CHK(e->own(e->fixed, &e->slow, (size_t)kSlowCap * sizeof(SlowRequest)));
+  CREATE_CHK(e->own(e->fixed, &e->xlocks, (size_t)kXLockCap * sizeof(XLock)));
+  CREATE_CHK(e->own(e->fixed, &e->sort_scratch, (size_t)kSlowSortCap * sizeof(unsigned long long) +
                                                (size_t)kSlowPlanCap * sizeof(SlowPlan)));  // sort keys | plans
-  CREATE_CHK(hipMalloc(&e->serial_scratch, (size_t)kSerialLdsBytes));
-  CREATE_CHK(hipMalloc(&e->masks, (size_t)e->nwg * kVisWG * 8));
-  CREATE_CHK(hipMalloc(&e->wg_count, (size_t)e->nwg * 4));
+  CREATE_CHK(e->own(e->fixed, &e->serial_scratch, (size_t)kSerialLdsBytes));
+  CREATE_CHK(e->own(e->fixed, &e->masks, (size_t)e->nwg * kVisWG * 8));
+  CREATE_CHK(e->own(e->fixed, &e->wg_count, (size_t)e->nwg * 4));
   // 8 per-XCD work lists; a segment = kFreshCap items for the list's new blocks (front_tail_role) in front of
   // room for every block of the pool (device_types.h: kFreshCap); queries use the buffer as one flat list
   e->seg_cap = (uint32_t)t.num_block + kFreshCap;
   e->vis_cap = kFreshCap + kNumLists * e->seg_cap;
-  CREATE_CHK(hipMalloc(&e->vis, (size_t)e->vis_cap * sizeof(VisItem)));
+  CREATE_CHK(e->own(e->fixed, &e->vis, (size_t)e->vis_cap * sizeof(VisItem)));
   for (int i = 0; i < 2; ++i) {
-    CREATE_CHK(hipMalloc(&e->del_list[i], (size_t)t.num_block * sizeof(DelItem)));
-    CREATE_CHK(hipMalloc(&e->upd_wg[i], kUpdCounters * 4));
+    CREATE_CHK(e->own(e->fixed, &e->del_list[i], (size_t)t.num_block * sizeof(DelItem)));
+    CREATE_CHK(e->own(e->fixed, &e->upd_wg[i], kUpdCounters * 4));
     CREATE_CHK(hipMemsetAsync(e->upd_wg[i], 0, kUpdCounters * 4, e->stream));
-    CREATE_CHK(hipMalloc(&e->slowdel[i], (size_t)kSlowDelCap * sizeof(SlowDelete)));
+    CREATE_CHK(e->own(e->fixed, &e->slowdel[i], (size_t)kSlowDelCap * sizeof(SlowDelete)));
   }
-  CREATE_CHK(hipMalloc(&e->win_ranks, (size_t)kFusedRank * 4));
-  CREATE_CHK(hipMalloc(&t.dclaim, (size_t)t.num_bucket * 4));
+  CREATE_CHK(e->own(e->fixed, &e->win_ranks, (size_t)kFusedRank * 4));
+  CREATE_CHK(e->own(e->fixed, &t.dclaim, (size_t)t.num_bucket * 4));
   CREATE_CHK(hipMemsetAsync(t.dclaim, 0xFF, (size_t)t.num_bucket * 4, e->stream));
   e->dwords = (e->dwords + kGroupWords - 1) / kGroupWords * kGroupWords;
   const uint32_t dsum_words = (e->dwords / kGroupWords + 31) / 32;
-  CREATE_CHK(hipMalloc(&e->dbitmap, (size_t)e->dwords * 4));
-  CREATE_CHK(hipMalloc(&e->dsummary, (size_t)dsum_words * 4));
-  CREATE_CHK(hipMalloc(&e->dprefix, (size_t)e->dwords * 4));
-  CREATE_CHK(hipMalloc(&e->cand_count, 2 * kCandSegs * kCandCountStride * 4));
+  CREATE_CHK(e->own(e->fixed, &e->dbitmap, (size_t)e->dwords * 4));
+  CREATE_CHK(e->own(e->fixed, &e->dsummary, (size_t)dsum_words * 4));
+  CREATE_CHK(e->own(e->fixed, &e->dprefix, (size_t)e->dwords * 4));
+  CREATE_CHK(e->own(e->fixed, &e->cand_count, 2 * kCandSegs * kCandCountStride * 4));
   CREATE_CHK(hipMemsetAsync(e->cand_count, 0, 2 * kCandSegs * kCandCountStride * 4, e->stream));
   for (int i = 0; i < 2; ++i) e->cand[i].count = e->cand_count + i * kCandSegs * kCandCountStride;
   // voxel memory starts zeroed (defined value for the reference's uninitialised rgb)
@@ -1270,11 +1279,7 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
     delete e;
     return RATSDF_ERR_DEVICE;
   }
-  if (e->upload_record() != RATSDF_OK) {
-    e->free_all();
-    delete e;
-    return RATSDF_ERR_DEVICE;
-  }
+  CREATE_CHK(e->upload_record());
 #undef CREATE_CHK
   *out = e;
   return RATSDF_OK;
@@ -1335,13 +1340,12 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
   if (e->use_graphs && n >= 2 && !sampled && !e->cand_ready && e->fused_serial && e->vpl != 1 &&
       (size_t)height * width * (size_t)e->S < 0xFFFFFFFFull) {
     const size_t npix = (size_t)height * width;
-    int st = e->ensure_image(npix, npix * (size_t)e->S);
-    if (st != RATSDF_OK) return st;
+    STCHK(e->ensure_image(npix, npix * (size_t)e->S));
     ratsdf_engine::BatchGraph* g = nullptr;
     if (e->batch_graph(n, height, width, &g) == RATSDF_OK && g) {
       const unsigned turn = g->turn++ & 1u;
       HIPCHK(hipEventSynchronize(g->ev[turn]));  // the copy that last used this staging table is done
-      FrameJob* hj = g->h_jobs[turn];
+      FrameJob* hj = g->h_jobs[turn].as<FrameJob>();
       for (int i = 0; i < n; ++i) {
         const ratsdf_engine::FrameIn in = input(i);
         FrameJob& j = hj[i];
@@ -1353,7 +1357,7 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
         j.par = (e->parity + (unsigned)i) & 1u;
         j.pad = 0;
       }
-      if (hipMemcpyAsync(g->d_jobs, hj, (size_t)n * sizeof(FrameJob), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+      if (hipMemcpyAsync(g->d_jobs.as<FrameJob>(), hj, (size_t)n * sizeof(FrameJob), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
           hipEventRecord(g->ev[turn], e->stream) != hipSuccess)
         return RATSDF_ERR_DEVICE;
       if (hipGraphLaunch(g->exec, e->stream) != hipSuccess) {
@@ -1393,8 +1397,7 @@ int ratsdf_prepare_device_batch(ratsdf_engine* e, int n, int height, int width) 
   if (!e || n < 0 || height <= 0 || width <= 0) return RATSDF_ERR_BAD_ARGUMENT;
   const size_t npix = (size_t)height * width;
   if (npix * (size_t)e->S >= 0xFFFFFFFFull) return RATSDF_ERR_BAD_ARGUMENT;
-  const int st = e->ensure_image(npix, npix * (size_t)e->S);
-  if (st != RATSDF_OK) return st;
+  STCHK(e->ensure_image(npix, npix * (size_t)e->S));
   if (e->use_graphs && n >= 2 && !e->cand_ready && e->fused_serial && e->vpl != 1) {
     ratsdf_engine::BatchGraph* g = nullptr;
     (void)e->batch_graph(n, height, width, &g);  // (a failed capture is remembered: such batches go frame by frame)
@@ -1412,8 +1415,7 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
   if (!finite_frame(*K, *T, max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   if (!ht || !lt) ht = lt = nullptr;  // modules/tsdf_module.cc:27-31
   const size_t npix = (size_t)height * width;
-  int st = e->ensure_stage(npix);
-  if (st != RATSDF_OK) return st;
+  STCHK(e->ensure_stage(npix));
   // The slots of the staging ring, one per call in turn (layout of a slot: depth | ht | lt | rgb).  The call
   // returns when the caller's images sit in the slot's page-locked memory: the upload runs on a copy stream
   // (it overlaps the previous frame's kernels), the frame's launches follow it on the engine's stream, and
@@ -1425,10 +1427,9 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
   // earlier calls, which are not waited for, may still be reading)
   const size_t slot_bytes = e->stage_pix * 16;
   const int slot = (int)(e->stage_no++ % kStageSlots);
-  uint8_t* h = e->h_stage + (size_t)slot * slot_bytes;
-  uint8_t* d = e->d_stage + (size_t)slot * slot_bytes;
+  uint8_t* h = e->h_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
+  uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
   HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // (an event never recorded counts as complete)
-  if (!e->copy_pool) e->copy_pool = new (std::nothrow) HostCopyPool(3);
   HostCopyPool::Piece pieces[8];
   int np = 0;
   auto add = [&](size_t off, const void* src, size_t bytes, int parts) {  // `parts` pieces of ~equal size
@@ -1445,8 +1446,8 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
     add(0, depth, npix * 4, 2);
     add(npix * 12, rgb, npix * 3, 2);
   }
-  if (e->copy_pool) {
-    e->copy_pool->copy(pieces, np);
+  if (HostCopyPool* cp = e->host_copy_pool()) {
+    cp->copy(pieces, np);
   } else {
     for (int i = 0; i < np; ++i) memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes);
   }
@@ -1473,7 +1474,7 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
     return fail(RATSDF_ERR_DEVICE);
   const ratsdf_engine::FrameIn in{d + npix * 12, d, ht ? d + npix * 4 : nullptr,
                                   ht ? d + npix * 8 : nullptr, K, T};
-  st = e->frame(in, nullptr, height, width, max_depth);
+  int st = e->frame(in, nullptr, height, width, max_depth);
   if (st != RATSDF_OK) return fail(st);
   if (hipEventRecord(e->use_ev[slot], e->stream) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
   if (!e->sync_integrate) return RATSDF_OK;
@@ -1525,7 +1526,7 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
         ++run;
     *took = run;
     hipStream_t cs = ((copy_no++ & 1) && two_streams) ? e->copy_stream2 : e->copy_stream;
-    uint8_t* d = e->d_stage + (size_t)slot * slot_bytes;
+    uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
     // (the slot's last reader: a frame of this call or of an earlier one; an event never recorded counts as complete)
     for (int j = 0; j < run; ++j) HIPCHK(hipStreamWaitEvent(cs, e->use_ev[slot + j], 0));
     const uint8_t* h0 = reinterpret_cast<const uint8_t*>(depth[i]);
@@ -1539,7 +1540,7 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
       }
       HIPCHK(hipMemcpyAsync(d + npix * 12, rgb[i], npix * 3, hipMemcpyHostToDevice, cs));
     } else {
-      uint8_t* h = e->h_stage + (size_t)slot * slot_bytes;
+      uint8_t* h = e->h_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
       HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // the slot's last upload has left its page-locked memory
       // (the frame's images side by side, by the engine's copy helpers: HostCopyPool)
       HostCopyPool::Piece pieces[4];
@@ -1550,9 +1551,8 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
         pieces[np++] = HostCopyPool::Piece{h + npix * 8, lt[i], npix * 4};
       }
       pieces[np++] = HostCopyPool::Piece{h + npix * 12, rgb[i], npix * 3};
-      if (!e->copy_pool) e->copy_pool = new (std::nothrow) HostCopyPool(3);
-      if (e->copy_pool) {
-        e->copy_pool->copy(pieces, np);
+      if (HostCopyPool* cp = e->host_copy_pool()) {
+        cp->copy(pieces, np);
       } else {
         for (int q = 0; q < np; ++q) memcpy(pieces[q].dst, pieces[q].src, pieces[q].bytes);
       }
@@ -1567,7 +1567,7 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
     return RATSDF_OK;
   };
   auto input = [&](int i) {
-    uint8_t* d = e->d_stage + (size_t)slot_of(i) * slot_bytes;
+    uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot_of(i) * slot_bytes;
     return ratsdf_engine::FrameIn{d + npix * 12, d, sem(i) ? d + npix * 4 : nullptr,
                                   sem(i) ? d + npix * 8 : nullptr, &K[i], &T[i]};
   };
@@ -1635,7 +1635,7 @@ int ratsdf_host_alloc(size_t bytes, void** out) {
   if (!out) return RATSDF_ERR_BAD_ARGUMENT;
   *out = nullptr;
   if (bytes == 0) return RATSDF_OK;
-  HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));  // (the caller's from here on: ratsdf_host_free)
   return RATSDF_OK;
 }
 
@@ -1677,12 +1677,11 @@ static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   const uint32_t occ_words = (t.num_entry + 63) / 64;
   const size_t nb = (size_t)t.num_block;
   const uint32_t ntiles = (uint32_t)((nb + kScanTile - 1) / kScanTile);
-  uint32_t* tmp = nullptr;  // unused flags | positions | tile sums | total
-  HIPCHK(hipMalloc(&tmp, (2 * nb + ntiles + 2) * 4));
-  uint32_t *unused = tmp, *pos = tmp + nb, *tiles = pos + nb, *d_total = tiles + ntiles + 1;
-  auto fail = [&](int st) {
+  DevMem tmp;  // unused flags | positions | tile sums | total
+  STCHK(tmp.alloc((2 * nb + ntiles + 2) * 4));
+  uint32_t *unused = tmp.as<uint32_t>(), *pos = unused + nb, *tiles = pos + nb, *d_total = tiles + ntiles + 1;
+  auto fail = [&](int st) {  // (nothing queued may outlive `tmp`)
     (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(tmp);
     return st;
   };
 #define REC_CHK(expr) do { if ((expr) != hipSuccess) return fail(RATSDF_ERR_DEVICE); } while (0)
@@ -1727,7 +1726,6 @@ static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   e->h_err[0] = e->h_err[1] = 0u;
   e->pending = false;
   e->cand_ready = false;
-  (void)hipFree(tmp);
   return RATSDF_OK;
 }
 
@@ -1812,6 +1810,8 @@ int ratsdf_last_frame_stats(ratsdf_engine* e, ratsdf_frame_stats* out) {
 extern "C" int ratsdf_debug_wave_stamps(ratsdf_engine* e, int enable) {
   DeviceGuard guard(e ? e->device : -1);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  // (one buffer per PROCESS, deliberately never freed and so without an owner: an engine's Ctl::debug_buf keeps
+  // pointing at it, and a static owner's destructor would call into a HIP runtime that is already shutting down)
   static unsigned long long* buf = nullptr;
   const size_t n = 16384 * 8;
   if (enable > 0) {
@@ -2018,18 +2018,7 @@ int ratsdf_pipeline_counters(ratsdf_engine* e, int64_t* out4, int reset) {
 // Device and page-locked staging buffers of the query-side downloads: kept between calls and only
 // ever grown (a hipMalloc / hipFree pair and a pageable D2H copy per Query cost more than the kernels).
 static int ensure_download_buffers(ratsdf_engine* e, size_t bytes) {
-  if (bytes <= e->dl_cap) return RATSDF_OK;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  if (e->dl_dev) (void)hipFree(e->dl_dev);
-  if (e->dl_host) (void)hipHostFree(e->dl_host);
-  e->dl_dev = nullptr;
-  e->dl_host = nullptr;
-  e->dl_cap = 0;
-  const size_t cap = bytes + bytes / 4;
-  HIPCHK(hipMalloc(&e->dl_dev, cap));
-  HIPCHK(hipHostMalloc(&e->dl_host, cap, hipHostMallocDefault));
-  e->dl_cap = cap;
-  return RATSDF_OK;
+  return e->grow_pair(e->dl_dev, e->dl_host, bytes, bytes + bytes / 4);
 }
 
 static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t* n) {
@@ -2045,7 +2034,8 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
       free(host);
       return st;
     }
-    float* dev = static_cast<float*>(e->dl_dev);
+    float* dev = e->dl_dev.as<float>();
+    const uint8_t* dl_host = e->dl_host.as<uint8_t>();
     const unsigned grid = cnt < 4096u ? (cnt + 3) / 4 : 1024u;
     if (semantic)
       hipLaunchKernelGGL(k_download<true>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
@@ -2053,7 +2043,7 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
     else
       hipLaunchKernelGGL(k_download<false>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
                          &e->ctl->n_sel, e->vs, dev);
-    hipError_t err = hipMemcpyAsync(e->dl_host, dev, total * rec, hipMemcpyDeviceToHost, e->stream);
+    hipError_t err = hipMemcpyAsync(e->dl_host.as<void>(), dev, total * rec, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (err != hipSuccess) {
       free(host);
@@ -2063,18 +2053,16 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
     // by side: the destination is fresh memory, and first-touch page faults (10 k of them for the 41 MB of a
     // GatherValid on the bench map) are what the single-threaded copy spent most of its time on
     const size_t bytes = total * rec;
-    if (bytes >= ((size_t)4 << 20)) {
-      if (!e->copy_pool) e->copy_pool = new (std::nothrow) HostCopyPool(3);
-    }
-    if (bytes >= ((size_t)4 << 20) && e->copy_pool) {
+    HostCopyPool* cp = bytes >= ((size_t)4 << 20) ? e->host_copy_pool() : nullptr;
+    if (cp) {
       HostCopyPool::Piece pieces[16];
       int np = 0;
       const size_t step = ((bytes + 15) / 16 + 4095) & ~(size_t)4095;
       for (size_t o = 0; o < bytes; o += step)
-        pieces[np++] = HostCopyPool::Piece{(uint8_t*)host + o, (const uint8_t*)e->dl_host + o, std::min(step, bytes - o)};
-      e->copy_pool->copy(pieces, np);
+        pieces[np++] = HostCopyPool::Piece{(uint8_t*)host + o, dl_host + o, std::min(step, bytes - o)};
+      cp->copy(pieces, np);
     } else {
-      memcpy(host, e->dl_host, bytes);
+      memcpy(host, dl_host, bytes);
     }
   }
   *out = host;
@@ -2166,12 +2154,13 @@ static int raycast_rows_device(ratsdf_engine* e, const ratsdf_intrinsics* K, int
   const float ms = ceilf(max_depth / step_size);
   const int max_step = ms >= 2147483648.f ? 2147483647 : (int)ms;  // voxel_tsdf.cu:298
   // block-level occupancy of the map as it is now (kernels_raycast.h: empty space costs no directory probes)
-  if (!e->d_occ) HIPCHK(hipMalloc(&e->d_occ, (kOccWords + kCellWords) * 4));
-  HIPCHK(hipMemsetAsync(e->d_occ, 0, (kOccWords + kCellWords) * 4, e->stream));
-  hipLaunchKernelGGL(k_occupancy_build, dim3(256), dim3(256), 0, e->stream, e->tab, (const Ctl*)e->ctl, e->d_occ);
+  STCHK(e->d_occ.grow((kOccWords + kCellWords) * 4));
+  uint32_t* const d_occ = e->d_occ.as<uint32_t>();
+  HIPCHK(hipMemsetAsync(d_occ, 0, (kOccWords + kCellWords) * 4, e->stream));
+  hipLaunchKernelGGL(k_occupancy_build, dim3(256), dim3(256), 0, e->stream, e->tab, (const Ctl*)e->ctl, d_occ);
   hipLaunchKernelGGL(k_raycast, dim3((width + 15) / 16, (row1 - row0 + 15) / 16), dim3(256), 0, e->stream,
                      e->tab, e->pool, P, step_size, max_step, (uint32_t*)d_rgba, (uint32_t*)d_normal, row0, row1,
-                     (const uint32_t*)e->d_occ, e->ctl);
+                     (const uint32_t*)d_occ, e->ctl);
   HIPCHK(hipGetLastError());
   return RATSDF_OK;
 }
@@ -2193,23 +2182,14 @@ int ratsdf_raycast_rows(ratsdf_engine* e, const ratsdf_intrinsics* K, int height
   // The two images leave through buffers the engine keeps: device memory for the kernel's output and page-locked host
   // memory for the copy out (until round 5: a hipMalloc / hipFree pair per call and two copies into the caller's
   // pageable buffers through the runtime's staging path -- 0.84 ms per 640x480 rendering of which the kernel was half).
-  if (e->render_cap < bytes * 2) {
-    (void)hipStreamSynchronize(e->stream);
-    if (e->d_render) (void)hipFree(e->d_render);
-    if (e->h_render) (void)hipHostFree(e->h_render);
-    e->d_render = e->h_render = nullptr;
-    e->render_cap = 0;
-    HIPCHK(hipMalloc(&e->d_render, bytes * 2));
-    HIPCHK(hipHostMalloc(&e->h_render, bytes * 2, hipHostMallocDefault));
-    e->render_cap = bytes * 2;
-  }
-  uint8_t* d = e->d_render;
-  int st = raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, d, d + bytes);
-  if (st != RATSDF_OK) return st;
-  HIPCHK(hipMemcpyAsync(e->h_render, d, bytes * 2, hipMemcpyDeviceToHost, e->stream));
+  STCHK(e->grow_pair(e->d_render, e->h_render, bytes * 2, bytes * 2));
+  uint8_t* d = e->d_render.as<uint8_t>();
+  uint8_t* h = e->h_render.as<uint8_t>();
+  STCHK(raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, d, d + bytes));
+  HIPCHK(hipMemcpyAsync(h, d, bytes * 2, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));  // voxel_tsdf.cu:901
-  if (rgba) memcpy(rgba, e->h_render, bytes);
-  if (normal) memcpy(normal, e->h_render + bytes, bytes);
+  if (rgba) memcpy(rgba, h, bytes);
+  if (normal) memcpy(normal, h + bytes, bytes);
   return RATSDF_OK;
 }
 
@@ -2253,29 +2233,20 @@ int ratsdf_sample_points(ratsdf_engine* e, const float* xyz, size_t n, ratsdf_sa
   { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
   if (n == 0) return e->sticky();
   // points in and records out through buffers the engine keeps, grown on demand (as the ray cast's d_render /
-  // h_render); a failed grow leaves no capacity behind, so the next call tries again
+  // h_render); their capacity in points is what they hold
   const size_t chunk = std::min(n, kSampleChunk);
-  if (e->sample_cap < chunk) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_sample) (void)hipFree(e->d_sample);
-    if (e->h_sample) (void)hipHostFree(e->h_sample);
-    e->d_sample = e->h_sample = nullptr;
-    e->sample_cap = 0;
-    HIPCHK(hipMalloc(&e->d_sample, chunk * (kSampleRecord + kSamplePoint)));
-    HIPCHK(hipHostMalloc(&e->h_sample, chunk * (kSampleRecord + kSamplePoint), hipHostMallocDefault));
-    e->sample_cap = chunk;
-  }
-  const size_t cap = e->sample_cap;
-  uint8_t* d_rec = e->d_sample;
-  float* d_pts = (float*)(e->d_sample + cap * kSampleRecord);
-  uint8_t* h_rec = e->h_sample;
-  float* h_pts = (float*)(e->h_sample + cap * kSampleRecord);
+  const size_t per = kSampleRecord + kSamplePoint;
+  STCHK(e->grow_pair(e->d_sample, e->h_sample, chunk * per, chunk * per));
+  const size_t cap = e->d_sample.size() / per;
+  uint8_t* d_rec = e->d_sample.as<uint8_t>();
+  float* d_pts = (float*)(d_rec + cap * kSampleRecord);
+  uint8_t* h_rec = e->h_sample.as<uint8_t>();
+  float* h_pts = (float*)(h_rec + cap * kSampleRecord);
   for (size_t o = 0; o < n; o += chunk) {
     const size_t m = std::min(chunk, n - o);
     memcpy(h_pts, xyz + 3 * o, m * kSamplePoint);
     HIPCHK(hipMemcpyAsync(d_pts, h_pts, m * kSamplePoint, hipMemcpyHostToDevice, e->stream));
-    const int st = sample_launch(e, d_pts, m, d_rec);
-    if (st != RATSDF_OK) return st;
+    STCHK(sample_launch(e, d_pts, m, d_rec));
     HIPCHK(hipMemcpyAsync(h_rec, d_rec, m * kSampleRecord, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     memcpy(out + o, h_rec, m * kSampleRecord);
@@ -2316,18 +2287,16 @@ static bool esdf_box(const int32_t* origin, const int32_t* dims, float occupied_
   return true;
 }
 
-// a workspace for n voxels; a failed grow leaves no capacity behind, so the next call tries again
+// a workspace for n voxels (laid out for the number it was allocated for)
 static int esdf_workspace(ratsdf_engine* e, size_t n, EsdfWork* w) {
   if (e->esdf_cap < n) {
     HIPCHK(hipStreamSynchronize(e->stream));  // an earlier field may still be using the old one
-    if (e->d_esdf) (void)hipFree(e->d_esdf);
-    e->d_esdf = nullptr;
     e->esdf_cap = 0;
-    HIPCHK(hipMalloc(&e->d_esdf, esdf_work_bytes(n)));
+    STCHK(e->d_esdf.alloc(esdf_work_bytes(n)));
     e->esdf_cap = n;
   }
   const size_t cap = e->esdf_cap;
-  uint8_t* p = e->d_esdf;
+  uint8_t* p = e->d_esdf.as<uint8_t>();
   w->st = p;
   w->gx = (uint32_t*)(p += esdf_round(cap));
   w->gy = (uint2*)(p += esdf_round(4 * cap));
@@ -2385,23 +2354,18 @@ int ratsdf_esdf(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3]
   { const int st0 = sticky_raised(e); if (st0 != RATSDF_OK) return st0; }
   EsdfWork w;
   { const int st0 = esdf_workspace(e, n, &w); if (st0 != RATSDF_OK) return st0; }
-  if (e->h_esdf_cap < kEsdfHostChunk) {  // (freed and regrown like the workspace)
-    if (e->h_esdf) (void)hipHostFree(e->h_esdf);
-    e->h_esdf = nullptr;
-    e->h_esdf_cap = 0;
-    HIPCHK(hipHostMalloc(&e->h_esdf, kEsdfHostChunk, hipHostMallocDefault));
-    e->h_esdf_cap = kEsdfHostChunk;
-  }
+  STCHK(e->h_esdf.grow(kEsdfHostChunk));
+  uint8_t* const h = e->h_esdf.as<uint8_t>();
   // the field lands in the x pass's buffer, dead once the y pass has run
   { const int st0 = esdf_launch(e, b, n, occupied_below, flags, w, (float*)w.gx, nullptr); if (st0 != RATSDF_OK) return st0; }
   const struct { const uint8_t* src; uint8_t* dst; size_t bytes; } parts[2] = {
       {(const uint8_t*)w.gx, (uint8_t*)out, n * sizeof(float)}, {w.st, state, state ? n : 0}};
   for (const auto& p : parts)
-    for (size_t o = 0; o < p.bytes; o += e->h_esdf_cap) {
-      const size_t m = std::min(e->h_esdf_cap, p.bytes - o);
-      HIPCHK(hipMemcpyAsync(e->h_esdf, p.src + o, m, hipMemcpyDeviceToHost, e->stream));
+    for (size_t o = 0; o < p.bytes; o += kEsdfHostChunk) {
+      const size_t m = std::min(kEsdfHostChunk, p.bytes - o);
+      HIPCHK(hipMemcpyAsync(h, p.src + o, m, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
-      memcpy(p.dst + o, e->h_esdf, m);
+      memcpy(p.dst + o, h, m);
     }
   return e->sticky();
 }
@@ -2443,15 +2407,17 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
   const size_t nts = (size_t)nb * 512 * 5;          // candidate triangles
   if (!e->d_mc) {
     const McTables h = make_mc_tables();
-    HIPCHK(hipMalloc(&e->d_mc, sizeof(McTables)));
-    HIPCHK(hipMemcpy(e->d_mc, &h, sizeof(McTables), hipMemcpyHostToDevice));
+    DevMem mc;  // (the engine keeps tables that have arrived, nothing else)
+    STCHK(mc.alloc(sizeof(McTables)));
+    HIPCHK(hipMemcpy(mc.as<void>(), &h, sizeof(McTables), hipMemcpyHostToDevice));
+    e->d_mc = std::move(mc);
   }
   // one scratch allocation: verts | vprob | vmask | vpos | tids | tmask | tpos | tile sums | total
   const size_t ntile_max = (nts > nvs ? nts : nvs) / kScanTile + 2;
   const size_t bytes = nvs * 12 + nvs * 4 * 3 + nts * 12 + nts * 4 * 2 + ntile_max * 4 + 64;
-  uint8_t* d = nullptr;
-  HIPCHK(hipMalloc(&d, bytes));
-  float* verts = (float*)d;
+  DevMem d;
+  STCHK(d.alloc(bytes));
+  float* verts = d.as<float>();
   float* vprob = verts + nvs * 3;
   uint32_t* vmask = (uint32_t*)(vprob + nvs);
   uint32_t* vpos = vmask + nvs;
@@ -2461,39 +2427,33 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
   uint32_t* tiles = tpos + nts;
   uint32_t* d_total = tiles + ntile_max;
   hipLaunchKernelGGL(k_marching_cubes, dim3(nb), dim3(512), 0, e->stream, e->tab, e->pool, e->vis,
-                     (const McTables*)e->d_mc, e->vs, verts, vprob, vmask, tids, tmask);
+                     e->d_mc.as<const McTables>(), e->vs, verts, vprob, vmask, tids, tmask);
   uint32_t nv = 0, nt = 0;
   st = mask_positions(e, vmask, nvs, vpos, tiles, d_total, &nv);
   if (st == RATSDF_OK) st = mask_positions(e, tmask, nts, tpos, tiles, d_total, &nt);
-  if (st != RATSDF_OK) {
-    (void)hipFree(d);
-    return st;
-  }
+  if (st != RATSDF_OK) return st;
   free(*vertices);
   free(*vertex_prob);
   free(*indices);
   *vertices = (float*)malloc((size_t)nv * 12 + 4);
   *vertex_prob = (float*)malloc((size_t)nv * 4 + 4);
   *indices = (int32_t*)malloc((size_t)nt * 12 + 4);
-  uint8_t* o = nullptr;
-  hipError_t err = hipMalloc(&o, (size_t)nv * 16 + (size_t)nt * 12 + 64);
-  if (err == hipSuccess) {
-    float* ov = (float*)o;
-    float* op = ov + (size_t)nv * 3;
-    int32_t* oi = (int32_t*)(op + nv);
-    hipLaunchKernelGGL(k_compact_vertices, dim3(2048), dim3(256), 0, e->stream, verts, vprob, vmask,
-                       vpos, nvs, ov, op);
-    hipLaunchKernelGGL(k_compact_triangles, dim3(2048), dim3(256), 0, e->stream, tids, tmask, tpos,
-                       vpos, nts, oi);
-    if (nv) err = hipMemcpyAsync(*vertices, ov, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess && nv)
-      err = hipMemcpyAsync(*vertex_prob, op, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess && nt)
-      err = hipMemcpyAsync(*indices, oi, (size_t)nt * 12, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    (void)hipFree(o);
-  }
-  (void)hipFree(d);
+  DevMem o;
+  STCHK(o.alloc((size_t)nv * 16 + (size_t)nt * 12 + 64));
+  float* ov = o.as<float>();
+  float* op = ov + (size_t)nv * 3;
+  int32_t* oi = (int32_t*)(op + nv);
+  hipLaunchKernelGGL(k_compact_vertices, dim3(2048), dim3(256), 0, e->stream, verts, vprob, vmask,
+                     vpos, nvs, ov, op);
+  hipLaunchKernelGGL(k_compact_triangles, dim3(2048), dim3(256), 0, e->stream, tids, tmask, tpos,
+                     vpos, nts, oi);
+  hipError_t err = hipSuccess;
+  if (nv) err = hipMemcpyAsync(*vertices, ov, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream);
+  if (err == hipSuccess && nv)
+    err = hipMemcpyAsync(*vertex_prob, op, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream);
+  if (err == hipSuccess && nt)
+    err = hipMemcpyAsync(*indices, oi, (size_t)nt * 12, hipMemcpyDeviceToHost, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   if (err != hipSuccess) return RATSDF_ERR_DEVICE;
   *n_vertices = nv;
   *n_triangles = nt;
@@ -2590,11 +2550,10 @@ int ratsdf_export_directory_delta_device(ratsdf_engine* e, void* d_payload, int3
 }
 
 // ---- test hooks ------------------------------------------------------------------------------
-static int upload_s3(ratsdf_engine* e, const int16_t* src, int32_t n, int16_t** dev) {
-  *dev = nullptr;
+static int upload_s3(ratsdf_engine* e, const int16_t* src, int32_t n, DevMem* dev) {
   if (n == 0) return RATSDF_OK;
-  HIPCHK(hipMalloc(dev, (size_t)n * 6));
-  HIPCHK(hipMemcpyAsync(*dev, src, (size_t)n * 6, hipMemcpyHostToDevice, e->stream));
+  STCHK(dev->alloc((size_t)n * 6));
+  HIPCHK(hipMemcpyAsync(dev->as<void>(), src, (size_t)n * 6, hipMemcpyHostToDevice, e->stream));
   return RATSDF_OK;
 }
 
@@ -2604,23 +2563,21 @@ int ratsdf_test_allocate(ratsdf_engine* e, const int16_t* bp, int32_t n) {
   if (!e || (!bp && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
   { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
   if (n == 0) return e->sticky();
-  int st = e->ensure_image(0, (size_t)n);
-  if (st != RATSDF_OK) return st;
-  int16_t* d = nullptr;
-  st = upload_s3(e, bp, n, &d);
-  if (st != RATSDF_OK) return st;
+  STCHK(e->ensure_image(0, (size_t)n));
+  DevMem d_bp;
+  STCHK(upload_s3(e, bp, n, &d_bp));
+  const int16_t* d = d_bp.as<int16_t>();
   FrameParams P = e->base_params();
   const uint32_t par = e->parity;  // an allocation pass of its own in the next frame's counters
   hipLaunchKernelGGL(k_alloc_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, P, d, n,
                      e->req, e->req_cap, e->slow, kSlowCap, e->ctl, par);
-  st = e->alloc_rank((uint32_t)n, par);
+  const int st = e->alloc_rank((uint32_t)n, par);
   hipLaunchKernelGGL(k_commit_only, dim3(256), dim3(256), 0, e->stream, e->tab, e->pool, e->req,
                      e->req_cap, e->req_k, e->win_ranks, e->ctl, par);
   // no deletes in this pass; k_settle just zeroes the counters again
   hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par),
                      e->ctl, par, (ratsdf_frame_stats*)nullptr);
-  const int st2 = e->sticky();
-  (void)hipFree(d);
+  const int st2 = e->sticky();  // (synchronises: nothing queued outlives the uploaded list)
   return st != RATSDF_OK ? st : st2;
 }
 
@@ -2632,11 +2589,11 @@ static int import_from_device(ratsdf_engine* e, int32_t n, const int16_t* d_pos,
   e->ever_sem = true;  // (the blocks come with their probabilities: FrameParams::segm_live)
   int st = e->ensure_image(0, (size_t)n);
   if (st != RATSDF_OK) return st;
-  uint32_t* d_missing = nullptr;
-  if (hipMalloc(&d_missing, 4) != hipSuccess) return RATSDF_ERR_DEVICE;
-  auto cleanup = [&](int status) {
+  DevMem missing_mem;
+  STCHK(missing_mem.alloc(4));
+  uint32_t* const d_missing = missing_mem.as<uint32_t>();
+  auto cleanup = [&](int status) {  // (nothing queued may outlive d_missing)
     (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(d_missing);
     return status;
   };
   FrameParams P = e->base_params();
@@ -2673,18 +2630,16 @@ int ratsdf_import_blocks(ratsdf_engine* e, int32_t n, const int16_t* bp, const f
   if (!e || n < 0 || (n > 0 && (!bp || !tsdf || !rgbw || !prob))) return RATSDF_ERR_BAD_ARGUMENT;
   { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
   if (n == 0) return e->sticky();
-  int16_t* d_pos = nullptr;
-  uint8_t* d_vox = nullptr;
+  DevMem pos_mem, vox_mem;
   const size_t per = (size_t)n * 512 * 4;
-  int st = upload_s3(e, bp, n, &d_pos);
-  if (st != RATSDF_OK) return st;
-  auto cleanup = [&](int status) {
+  STCHK(upload_s3(e, bp, n, &pos_mem));
+  auto cleanup = [&](int status) {  // (nothing queued may outlive the two uploads)
     (void)hipStreamSynchronize(e->stream);
-    if (d_pos) (void)hipFree(d_pos);
-    if (d_vox) (void)hipFree(d_vox);
     return status;
   };
-  if (hipMalloc(&d_vox, per * 3) != hipSuccess) return cleanup(RATSDF_ERR_DEVICE);
+  if (vox_mem.alloc(per * 3) != RATSDF_OK) return cleanup(RATSDF_ERR_DEVICE);
+  const int16_t* d_pos = pos_mem.as<int16_t>();
+  uint8_t* d_vox = vox_mem.as<uint8_t>();
   if (hipMemcpyAsync(d_vox, tsdf, per, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
       hipMemcpyAsync(d_vox + per, rgbw, per, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
       hipMemcpyAsync(d_vox + 2 * per, prob, per, hipMemcpyHostToDevice, e->stream) != hipSuccess)
@@ -2735,17 +2690,15 @@ int ratsdf_test_delete(ratsdf_engine* e, const int16_t* bp, int32_t n) {
   const int32_t m = (int32_t)(uniq.size() / 3);
   if (m == 0) return e->sticky();
   if (m > e->tab.num_block) return RATSDF_ERR_BAD_ARGUMENT;
-  int16_t* d = nullptr;
-  int st = upload_s3(e, uniq.data(), m, &d);
-  if (st != RATSDF_OK) return st;
+  DevMem d_bp;
+  STCHK(upload_s3(e, uniq.data(), m, &d_bp));
+  const int16_t* d = d_bp.as<int16_t>();
   const uint32_t par = e->parity;
   hipLaunchKernelGGL(k_delete_list, dim3((m + 255) / 256), dim3(256), 0, e->stream, e->tab, d, m,
                      e->carve_bufs(par), e->ctl, par);
   hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par),
                      e->ctl, par, (ratsdf_frame_stats*)nullptr);
-  const int st2 = e->sticky();
-  (void)hipFree(d);
-  return st != RATSDF_OK ? st : st2;
+  return e->sticky();  // (synchronises: nothing queued outlives the uploaded list)
 }
 
 int ratsdf_test_retrieve(ratsdf_engine* e, const int16_t* pts, int32_t n, ratsdf_rgbw* rgbw,
@@ -2755,11 +2708,11 @@ int ratsdf_test_retrieve(ratsdf_engine* e, const int16_t* pts, int32_t n, ratsdf
   if (!e || (!pts && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
   { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
   if (n == 0) return RATSDF_OK;
-  int16_t* d = nullptr;
-  int st = upload_s3(e, pts, n, &d);
-  if (st != RATSDF_OK) return st;
-  uint8_t* o = nullptr;
-  HIPCHK(hipMalloc(&o, (size_t)n * 24));
+  DevMem d_pts, d_res;
+  STCHK(upload_s3(e, pts, n, &d_pts));
+  STCHK(d_res.alloc((size_t)n * 24));
+  const int16_t* d = d_pts.as<int16_t>();
+  uint8_t* o = d_res.as<uint8_t>();
   uint32_t* o_rgbw = (uint32_t*)o;
   float* o_tsdf = (float*)(o + (size_t)n * 4);
   float* o_prob = (float*)(o + (size_t)n * 8);
@@ -2773,8 +2726,6 @@ int ratsdf_test_retrieve(ratsdf_engine* e, const int16_t* pts, int32_t n, ratsdf
   if (tsdf) memcpy(tsdf, h.data() + (size_t)n * 4, (size_t)n * 4);
   if (prob) memcpy(prob, h.data() + (size_t)n * 8, (size_t)n * 4);
   if (blocks) memcpy(blocks, h.data() + (size_t)n * 12, (size_t)n * 12);
-  (void)hipFree(o);
-  (void)hipFree(d);
   return RATSDF_OK;
 }
 
@@ -2785,17 +2736,15 @@ int ratsdf_test_assign_rgbw(ratsdf_engine* e, const int16_t* pts, const ratsdf_r
   if (!e || ((!pts || !vals) && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
   { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
   if (n == 0) return RATSDF_OK;
-  int16_t* d = nullptr;
-  int st = upload_s3(e, pts, n, &d);
-  if (st != RATSDF_OK) return st;
-  uint32_t* v = nullptr;
-  HIPCHK(hipMalloc(&v, (size_t)n * 4));
+  DevMem d_pts, d_vals;
+  STCHK(upload_s3(e, pts, n, &d_pts));
+  STCHK(d_vals.alloc((size_t)n * 4));
+  const int16_t* d = d_pts.as<int16_t>();
+  uint32_t* v = d_vals.as<uint32_t>();
   HIPCHK(hipMemcpyAsync(v, vals, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(k_assign_rgbw, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, e->pool,
                      d, v, n);
   HIPCHK(hipStreamSynchronize(e->stream));
-  (void)hipFree(v);
-  (void)hipFree(d);
   return RATSDF_OK;
 }
 
@@ -2813,17 +2762,16 @@ int ratsdf_dump_directory(ratsdf_engine* e, int32_t** entry_index, ratsdf_block*
   int32_t* ei = (int32_t*)malloc(cnt ? (size_t)cnt * 4 : 1);
   ratsdf_block* bl = (ratsdf_block*)malloc(cnt ? (size_t)cnt * 12 : 1);
   if (cnt) {
-    Entry* d_b = nullptr;
-    int32_t* d_e = nullptr;
-    HIPCHK(hipMalloc(&d_b, (size_t)cnt * 12));
-    HIPCHK(hipMalloc(&d_e, (size_t)cnt * 4));
+    DevMem b_mem, e_mem;
+    STCHK(b_mem.alloc((size_t)cnt * 12));
+    STCHK(e_mem.alloc((size_t)cnt * 4));
+    Entry* d_b = b_mem.as<Entry>();
+    int32_t* d_e = e_mem.as<int32_t>();
     hipLaunchKernelGGL(k_export_entries, dim3(256), dim3(256), 0, e->stream, e->vis, &e->ctl->n_sel,
                        d_b, d_e, cnt, (int32_t*)nullptr, (Ctl*)nullptr);
     HIPCHK(hipMemcpyAsync(bl, d_b, (size_t)cnt * 12, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(ei, d_e, (size_t)cnt * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    (void)hipFree(d_b);
-    (void)hipFree(d_e);
   }
   *entry_index = ei;
   *blocks = bl;
@@ -2840,11 +2788,12 @@ int ratsdf_dump_voxels(ratsdf_engine* e, const int32_t* pool_idx, int32_t n, flo
   if (n == 0) return RATSDF_OK;
   for (int i = 0; i < n; ++i)
     if (pool_idx[i] < 0 || pool_idx[i] >= e->tab.num_block) return RATSDF_ERR_BAD_ARGUMENT;
-  int32_t* d_idx = nullptr;
-  uint8_t* d_out = nullptr;
+  DevMem idx_mem, out_mem;
   const size_t per = (size_t)n * 512 * 4;
-  HIPCHK(hipMalloc(&d_idx, (size_t)n * 4));
-  HIPCHK(hipMalloc(&d_out, per * 3));
+  STCHK(idx_mem.alloc((size_t)n * 4));
+  STCHK(out_mem.alloc(per * 3));
+  int32_t* d_idx = idx_mem.as<int32_t>();
+  uint8_t* d_out = out_mem.as<uint8_t>();
   HIPCHK(hipMemcpyAsync(d_idx, pool_idx, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(k_gather_voxels, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->pool, d_idx, n,
                      (float*)d_out, (uint32_t*)(d_out + per), (float*)(d_out + 2 * per));
@@ -2852,8 +2801,6 @@ int ratsdf_dump_voxels(ratsdf_engine* e, const int32_t* pool_idx, int32_t n, flo
   if (rgbw) HIPCHK(hipMemcpyAsync(rgbw, d_out + per, per, hipMemcpyDeviceToHost, e->stream));
   if (prob) HIPCHK(hipMemcpyAsync(prob, d_out + 2 * per, per, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  (void)hipFree(d_idx);
-  (void)hipFree(d_out);
   return RATSDF_OK;
 }
 
@@ -2901,14 +2848,10 @@ struct ratsdf_group {
   hipStream_t stream = nullptr;
   std::vector<hipEvent_t> ev_member;  // member stream -> group stream
   hipEvent_t ev_done = nullptr;       // group stream -> member streams
-  EngineDev* d_engs = nullptr;
-  FrameJob* d_jobs = nullptr;
-  size_t jobs_cap = 0;
+  DevMem d_engs, d_jobs;  // EngineDev[S]; FrameJob[frames of a batch x S], grown on demand
   // page-locked staging of the tables, two of each, used alternately (a copy may still be pending
   // when the next batch is being prepared)
-  EngineDev* h_engs[2] = {nullptr, nullptr};
-  FrameJob* h_jobs[2] = {nullptr, nullptr};
-  size_t h_jobs_cap = 0;
+  HostMem h_engs[2], h_jobs[2];
   hipEvent_t ev_stage[2] = {nullptr, nullptr};
   unsigned batch_no = 0;
   int split_a = 100, split_b = 0;  // look-ahead share of k_front / k_alloc_rank (rest: k_integrate)
@@ -2933,11 +2876,10 @@ struct ratsdf_group {
   }
   void free_all() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (d_engs) (void)hipFree(d_engs);
-    if (d_jobs) (void)hipFree(d_jobs);
+    for (DevMem* m : {&d_engs, &d_jobs}) m->reset();
     for (int i = 0; i < 2; ++i) {
-      if (h_engs[i]) (void)hipHostFree(h_engs[i]);
-      if (h_jobs[i]) (void)hipHostFree(h_jobs[i]);
+      h_engs[i].reset();
+      h_jobs[i].reset();
       if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
     }
     for (auto& ev : ev_member)
@@ -2997,9 +2939,9 @@ int ratsdf_group_create(ratsdf_engine* const* engines, int n, ratsdf_group** out
     }                                                                    \
   } while (0)
   GROUP_CHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-  GROUP_CHK(hipMalloc(&g->d_engs, (size_t)n * sizeof(EngineDev)));
+  GROUP_CHK(g->d_engs.alloc((size_t)n * sizeof(EngineDev)));
   for (int i = 0; i < 2; ++i) {
-    GROUP_CHK(hipHostMalloc(&g->h_engs[i], (size_t)n * sizeof(EngineDev), hipHostMallocDefault));
+    GROUP_CHK(g->h_engs[i].alloc((size_t)n * sizeof(EngineDev)));
     GROUP_CHK(hipEventCreateWithFlags(&g->ev_stage[i], hipEventDisableTiming));
   }
   for (int i = 0; i < n; ++i)
@@ -3044,32 +2986,22 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   if (npix * (size_t)e0->S >= 0xFFFFFFFFull) return RATSDF_ERR_BAD_ARGUMENT;
   for (ratsdf_engine* e : g->eng) {
     if (e->cand_ready) return RATSDF_ERR_BAD_ARGUMENT;  // cannot happen between complete calls
-    const int st = e->ensure_image(npix, npix * (size_t)e->S);
-    if (st != RATSDF_OK) return st;
+    STCHK(e->ensure_image(npix, npix * (size_t)e->S));
   }
   // ---- tables ----
   const unsigned slot = g->batch_no++ & 1u;
   const size_t njobs = (size_t)n * S;
-  if (njobs > g->jobs_cap) {
+  const size_t job_bytes = njobs * sizeof(FrameJob);
+  if (job_bytes > g->d_jobs.size() || job_bytes > g->h_jobs[0].size() || job_bytes > g->h_jobs[1].size()) {
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (g->d_jobs) (void)hipFree(g->d_jobs);
-    g->d_jobs = nullptr;
-    g->jobs_cap = 0;
-    HIPCHK(hipMalloc(&g->d_jobs, njobs * sizeof(FrameJob)));
-    g->jobs_cap = njobs;
+    STCHK(g->d_jobs.grow(job_bytes));
+    for (int i = 0; i < 2; ++i) STCHK(g->h_jobs[i].grow(job_bytes));
   }
-  if (njobs > g->h_jobs_cap) {
-    HIPCHK(hipStreamSynchronize(g->stream));
-    for (int i = 0; i < 2; ++i) {
-      if (g->h_jobs[i]) (void)hipHostFree(g->h_jobs[i]);
-      g->h_jobs[i] = nullptr;
-      HIPCHK(hipHostMalloc(&g->h_jobs[i], njobs * sizeof(FrameJob), hipHostMallocDefault));
-    }
-    g->h_jobs_cap = njobs;
-  }
+  FrameJob* const d_jobs = g->d_jobs.as<FrameJob>();
+  EngineDev* const d_engs = g->d_engs.as<EngineDev>();
   HIPCHK(hipEventSynchronize(g->ev_stage[slot]));  // the copy that last used this staging pair is done
-  for (int s = 0; s < S; ++s) g->h_engs[slot][s] = g->eng[(size_t)s]->record();
-  FrameJob* hj = g->h_jobs[slot];
+  for (int s = 0; s < S; ++s) g->h_engs[slot].as<EngineDev>()[s] = g->eng[(size_t)s]->record();
+  FrameJob* hj = g->h_jobs[slot].as<FrameJob>();
   for (int f = 0; f < n; ++f)
     for (int s = 0; s < S; ++s) {
       const size_t i = (size_t)f * S + s;
@@ -3092,13 +3024,13 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
     HIPCHK(hipEventRecord(g->ev_member[(size_t)s], g->eng[(size_t)s]->stream));
     HIPCHK(hipStreamWaitEvent(g->stream, g->ev_member[(size_t)s], 0));
   }
-  HIPCHK(hipMemcpyAsync(g->d_engs, g->h_engs[slot], (size_t)S * sizeof(EngineDev),
+  HIPCHK(hipMemcpyAsync(d_engs, g->h_engs[slot].as<EngineDev>(), (size_t)S * sizeof(EngineDev),
                         hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipMemcpyAsync(g->d_jobs, hj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipMemcpyAsync(d_jobs, hj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, g->stream));
   HIPCHK(hipEventRecord(g->ev_stage[slot], g->stream));
 
   // ---- launches ----
-  EnginePtr engs = (EnginePtr)g->d_engs;
+  EnginePtr engs = (EnginePtr)d_engs;
   const bool fused = e0->fused_serial && e0->vpl != 1;
   const uint32_t n_serial_wg = fused ? 8u : 0u;
   ratsdf_engine::Geom g1 = e0->geometry(height, width, true, e0->vpl == 1 ? 100 : g->split_a,
@@ -3116,7 +3048,7 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
     all.first_tile = 0;
     all.n_tiles = g0.n_cand_wg * 4;
     hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, S), dim3(256), 0, g->stream, engs,
-                       (JobPtr)g->d_jobs, all);
+                       (JobPtr)d_jobs, all);
   }
   // A failure from here on leaves launches queued on the group's stream on behalf of members that do
   // not know about them: the members are brought to a consistent state before the error is returned
@@ -3155,8 +3087,8 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   for (int f = 0; f < n; ++f) {
     const bool has_next = f + 1 < n;
     const ratsdf_engine::Geom& gg = has_next ? g1 : g0;
-    JobPtr cur = (JobPtr)(g->d_jobs + (size_t)f * S);
-    JobPtr nxt = (JobPtr)(g->d_jobs + (size_t)(has_next ? f + 1 : f) * S);
+    JobPtr cur = (JobPtr)(d_jobs + (size_t)f * S);
+    JobPtr nxt = (JobPtr)(d_jobs + (size_t)(has_next ? f + 1 : f) * S);
 #ifdef RATSDF_STAMPS
     if (e0->tab.tail_on)
       hipLaunchKernelGGL(k_front_g<true>, dim3(gg.n_front_wg, S), dim3(256), 0, g->stream, engs, cur, nxt,
