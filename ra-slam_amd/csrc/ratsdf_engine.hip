@@ -22,6 +22,7 @@
 #include "kernels_mesh.h"
 #include "kernels_sample.h"
 #include "kernels_esdf.h"
+#include "kernels_fuse.h"
 #include "hip_mem.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
@@ -221,6 +222,7 @@ struct EngineMem {
   HostMem h_sample;
   DevMem d_esdf;       // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks (ratsdf_engine::esdf_cap)
   HostMem h_esdf;      // page-locked copy of the host entry point's results, passed through in chunks
+  DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
   DevMem dl_dev;       // query-side downloads (grow-only)
@@ -3192,3 +3194,4 @@ int ratsdf_group_profile_read(ratsdf_group* g, double* ms, int64_t* launches) {
 }  // extern "C"
 
 #include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)
+#include "fuse.inc"     // ratsdf_fuse_map / ratsdf_fuse_blocks[_device] / ratsdf_fuse_map_file (include/ratsdf_fuse.h)

@@ -47,6 +47,11 @@ struct Api {
   int (*sample_points)(ratsdf_engine*, const float*, size_t, ratsdf_sample*) = nullptr;
   // include/ratsdf_esdf.h: likewise optional (not in the CPU oracle)
   int (*esdf)(ratsdf_engine*, const int32_t*, const int32_t*, float, uint32_t, float*, uint8_t*) = nullptr;
+  // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
+  int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
+  int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
+                     ratsdf_fuse_stats*) = nullptr;
+  int (*fuse_map_file)(ratsdf_engine*, const char*, ratsdf_fuse_stats*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -106,6 +111,13 @@ class TSDFGrid {
   // (also kept in last_status()); no reference counterpart.
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);
+  // map fusion (include/ratsdf_fuse.h): another grid's map (same device, voxel size and truncation; only read), n
+  // blocks in ratsdf_import_blocks' layout, or a checkpoint file merged into this map with the weighted-average voxel
+  // update.  stats may be nullptr.  Return the status (also kept in last_status()); no reference counterpart.
+  int FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats = nullptr);
+  int FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw, const float* prob,
+                 ratsdf_fuse_stats* stats = nullptr);
+  int FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats = nullptr);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

@@ -148,6 +148,12 @@ class TSDFSystem {
   int LoadMap(const std::string& path);
   // TSDFGrid::SamplePoints under the engine's mutex, like Query: the map as integrated so far
   int Sample(const float* xyz, size_t n, ratsdf_sample* out);
+  // map fusion (include/ratsdf_fuse.h): Flush() first -- every frame queued so far is in the map before it is merged
+  // with another -- then under the engine's mutex, like SaveMap; return the status
+  int FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats = nullptr);
+  int FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw, const float* prob,
+                 ratsdf_fuse_stats* stats = nullptr);
+  int FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats = nullptr);
   // TSDFGrid::ESDF under the engine's mutex, like Sample
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);

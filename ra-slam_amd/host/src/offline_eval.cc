@@ -19,6 +19,7 @@
 //          [--threads N (decoder threads, default 4)]
 //          [--load-map FILE (a map checkpoint to continue, before the first frame; its voxel size must be --voxel)]
 //          [--first-frame K (skip the first K frames of the dataset)] [--save-map FILE (after the last frame)]
+//          [--fuse-map FILE (a checkpoint fused into the map after the last frame, before --save-map / the downloads)]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,7 +53,7 @@ int main(int argc, char** argv) {
   const char* lib = nullptr;
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
-  std::string download_all, download_mesh, dump_dir, load_map, save_map;
+  std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -76,6 +77,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump-raw-color") dump_raw_color = true;
     else if (a == "--load-map") load_map = next();
     else if (a == "--save-map") save_map = next();
+    else if (a == "--fuse-map") fuse_map = next();
     else if (a == "--first-frame") first_frame = atoi(next());
     else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -166,6 +168,18 @@ int main(int argc, char** argv) {
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
       fprintf(stderr, "[offline_eval] %d frames in %.3f s (%.1f frames/s; waited %.3f s for the decoders)\n", n, dt,
               n / dt, t_read);
+      if (!fuse_map.empty()) {  // map fusion (include/ratsdf_fuse.h): another session's checkpoint merged into this map
+        ratsdf_fuse_stats fs;
+        memset(&fs, 0, sizeof(fs));
+        const int st = tsdf->FuseMapFile(fuse_map, &fs);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --fuse-map %s: %s\n", fuse_map.c_str(), Api::Load(lib).status_string(st));
+          return 1;
+        }
+        fprintf(stderr, "[offline_eval] fused %lld blocks from %s (%lld new, %lld voxels copied, %lld averaged)\n",
+                (long long)fs.blocks_seen, fuse_map.c_str(), (long long)fs.blocks_allocated, (long long)fs.voxels_copied,
+                (long long)fs.voxels_averaged);
+      }
       if (!save_map.empty() && tsdf->SaveMap(save_map) != RATSDF_OK) return 1;
       if (!download_all.empty()) tsdf->DownloadAll(download_all);
       if (!download_mesh.empty())  // offline_eval.cc:95-98

@@ -78,6 +78,9 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.load_map = reinterpret_cast<decltype(api.load_map)>(opt_sym("load_map"));
   api.map_file_info = reinterpret_cast<decltype(api.map_file_info)>(opt_sym("map_file_info"));
   api.sample_points = reinterpret_cast<decltype(api.sample_points)>(opt_sym("sample_points"));
+  api.fuse_map = reinterpret_cast<decltype(api.fuse_map)>(opt_sym("fuse_map"));
+  api.fuse_blocks = reinterpret_cast<decltype(api.fuse_blocks)>(opt_sym("fuse_blocks"));
+  api.fuse_map_file = reinterpret_cast<decltype(api.fuse_map_file)>(opt_sym("fuse_map_file"));
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   return loaded.emplace(key, api).first->second;
 }
@@ -227,6 +230,27 @@ int TSDFGrid::LoadMap(const std::string& path) {
 int TSDFGrid::SamplePoints(const float* xyz, size_t n, ratsdf_sample* out) {
   if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   note(api_->sample_points ? api_->sample_points(engine_, xyz, n, out) : RATSDF_ERR_NOT_IMPLEMENTED, "SamplePoints");
+  return status_;
+}
+
+int TSDFGrid::FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats) {
+  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->fuse_map ? api_->fuse_map(engine_, src.engine_, stats) : RATSDF_ERR_NOT_IMPLEMENTED, "FuseMap");
+  return status_;
+}
+
+int TSDFGrid::FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw,
+                         const float* prob, ratsdf_fuse_stats* stats) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->fuse_blocks ? api_->fuse_blocks(engine_, n, block_pos, tsdf, rgbw, prob, stats) : RATSDF_ERR_NOT_IMPLEMENTED,
+       "FuseBlocks");
+  return status_;
+}
+
+int TSDFGrid::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
+  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->fuse_map_file ? api_->fuse_map_file(engine_, path.c_str(), stats) : RATSDF_ERR_NOT_IMPLEMENTED,
+       "FuseMapFile");
   return status_;
 }
 
@@ -495,6 +519,25 @@ int TSDFSystem::LoadMap(const std::string& path) {
   Flush();
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.LoadMap(path);
+}
+
+int TSDFSystem::FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.FuseMap(src, stats);
+}
+
+int TSDFSystem::FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw,
+                           const float* prob, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.FuseBlocks(n, block_pos, tsdf, rgbw, prob, stats);
+}
+
+int TSDFSystem::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.FuseMapFile(path, stats);
 }
 
 int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {

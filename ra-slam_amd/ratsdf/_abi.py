@@ -92,6 +92,12 @@ assert SAMPLE_DTYPE.itemsize == 32
 # include/ratsdf_esdf.h (Euclidean signed distance field over a box): handled like SAMPLE_SYMBOLS
 ESDF_SYMBOLS = ["esdf", "esdf_device"]
 ESDF_UNKNOWN_OCCUPIED = 1
+# include/ratsdf_fuse.h (map fusion): handled like SAMPLE_SYMBOLS
+FUSE_SYMBOLS = ["fuse_map", "fuse_blocks", "fuse_blocks_device", "fuse_map_file"]
+# ratsdf_fuse_stats (40 bytes)
+FUSE_STATS = np.dtype([("blocks_seen", "<i8"), ("blocks_allocated", "<i8"), ("blocks_skipped", "<i8"),
+                       ("voxels_copied", "<i8"), ("voxels_averaged", "<i8")])
+assert FUSE_STATS.itemsize == 40
 ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
 
 
@@ -223,6 +229,17 @@ class Library:
             else:
                 f.restype = C.c_int
                 f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_uint32, vp, vp]
+            self.fn[s] = f
+
+        for s in FUSE_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = {"fuse_map": [vp, vp, vp], "fuse_blocks": [vp, C.c_int32, vp, vp, vp, vp, vp],
+                              "fuse_blocks_device": [vp, C.c_int32, vp, vp, vp],
+                              "fuse_map_file": [vp, C.c_char_p, vp]}[s]
             self.fn[s] = f
 
     def backend(self):
@@ -646,6 +663,40 @@ class Engine:
         """import_blocks() from device buffers in export_blocks_device()'s layout (read on the engine's stream)"""
         _check(self.lib.fn["import_blocks_device"](self._h, int(n), d_block_pos or None, d_voxels or None),
                "import_blocks_device")
+
+    # -- map fusion (include/ratsdf_fuse.h) ------------------------------------------------
+    def _fuse(self, name, *args):
+        """calls a fusion entry point; returns its statistics as a dict (filled in even when the call fails: the
+        blocks fused before an error stay fused) -- raises RatsdfError carrying them as ``.fuse_stats``"""
+        st = np.zeros(1, dtype=FUSE_STATS)
+        rc = self.lib.fn[name](self._h, *args, st.ctypes.data)
+        stats = {k: int(st[0][k]) for k in FUSE_STATS.names}
+        if rc != 0:
+            err = RatsdfError(rc, name)
+            err.fuse_stats = stats
+            raise err
+        return stats
+
+    def fuse_map(self, src):
+        """merges the map of ``src`` (an Engine on the same device, same voxel size and truncation) into this map with
+        the weighted-average voxel update; ``src`` is only read.  Returns the statistics."""
+        return self._fuse("fuse_map", src._h)
+
+    def fuse_blocks(self, block_pos, tsdf, rgbw, prob):
+        """fuses blocks given as import_blocks() takes them (positions must be distinct)"""
+        a, n = self._s3(block_pos)
+        t = np.ascontiguousarray(tsdf, dtype=np.float32).reshape(n, BLOCK_VOLUME)
+        c = np.ascontiguousarray(rgbw, dtype=RGBW_DTYPE).reshape(n, BLOCK_VOLUME)
+        p = np.ascontiguousarray(prob, dtype=np.float32).reshape(n, BLOCK_VOLUME)
+        return self._fuse("fuse_blocks", n, a.ctypes.data, t.ctypes.data, c.ctypes.data, p.ctypes.data)
+
+    def fuse_blocks_device(self, n, d_block_pos, d_voxels):
+        """fuse_blocks() from device buffers in export_blocks_device()'s layout (positions must be distinct)"""
+        return self._fuse("fuse_blocks_device", int(n), d_block_pos or None, d_voxels or None)
+
+    def fuse_map_file(self, path):
+        """fuses a checkpoint written by save_map() into this map (only voxel size and truncation must agree)"""
+        return self._fuse("fuse_map_file", os.fsencode(path))
 
     # -- test hooks ------------------------------------------------------------------------
     @staticmethod

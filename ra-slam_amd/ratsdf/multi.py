@@ -821,3 +821,26 @@ def raycast_across_shards(engine, make_scratch, per_rank, intrinsics, height, wi
     got = _gather_arrays([mine[0].reshape(-1), mine[1].reshape(-1)], world, device)
     return (np.concatenate([g[0].reshape(-1, width, 4) for g in got], axis=0),
             np.concatenate([g[1].reshape(-1, width, 4) for g in got], axis=0))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Map fusion across engines (include/ratsdf_fuse.h): the members of a Group end with one map each of one scene; this
+# brings them together with the engine's weighted-average voxel update.  (Across ranks: not built yet -- the root would
+# take every rank's export_blocks_device rows from an all-gather and hand them to Engine.fuse_blocks_device.)
+# ---------------------------------------------------------------------------------------------------------------
+FUSE_STAT_KEYS = ("blocks_seen", "blocks_allocated", "blocks_skipped", "voxels_copied", "voxels_averaged")
+
+
+def _add_stats(total, part):
+    for k in FUSE_STAT_KEYS:
+        total[k] += part[k]
+
+
+def fuse_group(engines):
+    """the maps of engines[1:] fused into engines[0] (members of a Group, or any engines of one device with the same
+    voxel size and truncation): a chain of ratsdf_fuse_map, voxel data never leaves the device.  The sources are only
+    read.  Returns the summed statistics."""
+    total = dict.fromkeys(FUSE_STAT_KEYS, 0)
+    for src in engines[1:]:
+        _add_stats(total, engines[0].fuse_map(src))
+    return total
