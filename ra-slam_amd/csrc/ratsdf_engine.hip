@@ -239,6 +239,80 @@ struct EngineMem {
   }
 };
 
+// Timing of the dominant kernel (k_integrate / k_integrate_g) with HIP events attached to the dispatch itself; an
+// engine and a group each hold one.
+struct KernelTimer {
+  bool on = false;
+  int mode = 1;  // 1: every 4th frame, sums only; 2 (engines): every frame, per-frame records
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+  size_t used = 0;
+  uint64_t frame = 0;
+  double ms = 0;
+  int64_t n = 0;
+  std::vector<float> k_us, period_us;  // mode 2: kernel time of a frame / start-to-start period
+
+  // pairs for the next `k` timed frames exist afterwards (what may fail, apart from the launches)
+  int reserve(size_t k) {
+    while (prof_events.size() < used + k) {
+      hipEvent_t a, b;
+      HIPCHK(hipEventCreate(&a));
+      if (hipEventCreate(&b) != hipSuccess) {
+        (void)hipEventDestroy(a);
+        return RATSDF_ERR_DEVICE;
+      }
+      prof_events.emplace_back(a, b);
+    }
+    return RATSDF_OK;
+  }
+  // the events of the next frame's launch: a pair when the frame is one of the timed ones, nulls (= a plain launch)
+  // otherwise (sampled: events perturb the stream; mode 2 times every frame, for latency distributions)
+  std::pair<hipEvent_t, hipEvent_t> take() {
+    if (!on || (mode != 2 && frame++ % 4 != 0) || used == prof_events.size()) return {nullptr, nullptr};
+    return prof_events[used++];
+  }
+  bool full() const { return on && used >= (mode == 2 ? 60000u : 4096u); }
+  // `final`: nothing follows the timed frames (a read-out).  An intermediate drain in mode 2 (the event pool is
+  // full) keeps the LAST pair for the next drain: its period ends at the start of a frame that has not been
+  // launched yet, and k_us / period_us must stay index-aligned (ratsdf_profile_read_frames).
+  int drain(hipStream_t stream, bool final = true) {
+    if (!used) return RATSDF_OK;
+    HIPCHK(hipStreamSynchronize(stream));
+    const bool keep_last = mode == 2 && !final && used > 1;
+    const size_t cnt = keep_last ? used - 1 : used;
+    for (size_t i = 0; i < cnt; ++i) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, prof_events[i].first, prof_events[i].second));
+      ms += t;
+      ++n;
+      if (mode == 2) {
+        k_us.push_back(t * 1e3f);
+        float gap = 0;  // consecutive frames: start of this frame's k_integrate to the next one's (last frame: 0)
+        if (i + 1 < used) HIPCHK(hipEventElapsedTime(&gap, prof_events[i].first, prof_events[i + 1].first));
+        period_us.push_back(gap * 1e3f);
+      }
+    }
+    if (keep_last) std::swap(prof_events[0], prof_events[used - 1]);
+    used = keep_last ? 1 : 0;
+    return RATSDF_OK;
+  }
+  // the sums since the last read-out
+  int read(hipStream_t stream, double* ms_out, int64_t* launches) {
+    const int st = drain(stream);
+    if (ms_out) *ms_out = ms;
+    if (launches) *launches = n;
+    ms = 0;
+    n = 0;
+    return st;
+  }
+  void destroy() {
+    for (auto& ev : prof_events) {
+      (void)hipEventDestroy(ev.first);
+      (void)hipEventDestroy(ev.second);
+    }
+    prof_events.clear();
+  }
+};
+
 struct ratsdf_engine : EngineMem {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -385,16 +459,8 @@ struct ratsdf_engine : EngineMem {
   };
   std::vector<GraphShape> graph_failed;  // shapes whose capture failed once: launched frame by frame from then on
 
-  // profiling of the dominant kernel
-  bool profiling = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-  size_t prof_used = 0;
-  uint64_t prof_frame = 0;
-  uint64_t prof_batch = 0;
-  double prof_ms = 0;
-  int64_t prof_n = 0;
-  int prof_mode = 1;                     // 1: every 4th frame, sums only; 2: every frame, per-frame records
-  std::vector<float> prof_k_us, prof_period_us;  // mode 2: kernel time of a frame / start-to-start period
+  KernelTimer timer;         // profiling of the dominant kernel
+  uint64_t prof_batch = 0;   // (mode 1: every fourth batch carries the events, ratsdf_integrate_device_batch)
 
   int free_all();
   int ensure_image(size_t npix, size_t nranks);
@@ -404,26 +470,52 @@ struct ratsdf_engine : EngineMem {
   RankBufs rank_bufs(uint32_t nranks) const;
   int alloc_rank(uint32_t nranks, unsigned par, const CandJob* next = nullptr, bool frame = false);
   int settle();
-  void abandon_pipeline();
+  void abandon_pipeline(int frames_launched = 0, bool clear_next = false);
   CarveBufs carve_bufs(unsigned par) const;
   int select(int mode, const GridBounds& gb, uint32_t* count_slot);
   struct FrameIn {
     const void *rgb, *depth, *ht, *lt;
     const ratsdf_intrinsics* K;
     const ratsdf_pose* T;
+    // ht and lt count only together (modules/tsdf_module.cc:27-31)
+    static FrameIn of(const void* rgb, const void* depth, const void* ht, const void* lt, const ratsdf_intrinsics* K,
+                      const ratsdf_pose* T) {
+      if (!ht || !lt) ht = lt = nullptr;
+      return FrameIn{rgb, depth, ht, lt, K, T};
+    }
+    // ... element i of a batch's arrays (`ht` / `lt`: the arrays themselves may be missing)
+    static FrameIn at(size_t i, const void* const* rgb, const void* const* depth, const void* const* ht,
+                      const void* const* lt, const ratsdf_intrinsics* K, const ratsdf_pose* T) {
+      return of(rgb[i], depth[i], ht ? ht[i] : nullptr, lt ? lt[i] : nullptr, &K[i], &T[i]);
+    }
   };
   FrameParams frame_params(const FrameIn& in, int H, int W, float md) const;
+  void fill_job(FrameJob& j, const FrameIn& in, int H, int W, float md, unsigned par) const;
   CandJob cand_job(const FrameIn& in, const FrameParams& P, unsigned par) const;
   int frame(const FrameIn& cur, const FrameIn* next, int H, int W, float md);
   int sticky();
   int read_small(void* dst, const void* dev_src, size_t bytes);
-  int drain_profile(bool final = true);
   FrameParams base_params() const;
   struct Geom {
     unsigned n_vis_wg, parts, n_front_wg, n_cand_wg, grid;
     AheadGeom a, b, c;  // look-ahead shares of k_front, k_alloc_rank, k_integrate
   };
   Geom geometry(int H, int W, bool has_next, int split_a, int split_b) const;
+  int lookahead_split(size_t npix) const;
+  bool graph_eligible(int n, int H, int W) const;
+  // A slot of the staging ring (depth | ht | lt | rgb, 16 bytes per pixel of the ring's largest image): its
+  // page-locked and its device memory, for an image of npix pixels.
+  struct StageSlot {
+    uint8_t *h, *d;
+    size_t npix;
+    FrameIn input(const ratsdf_intrinsics* K, const ratsdf_pose* T, bool sem) const {
+      return FrameIn{d + npix * 12, d, sem ? d + npix * 4 : nullptr, sem ? d + npix * 8 : nullptr, K, T};
+    }
+  };
+  StageSlot stage_slot(int slot, size_t npix) const;
+  void stage_fill(const StageSlot& s, const void* rgb, const void* depth, const void* ht, const void* lt, int parts);
+  int stage_upload(const StageSlot& s, bool sem, hipStream_t cs);
+  int stage_fail(int status);
 };
 
 FrameParams ratsdf_engine::base_params() const {
@@ -466,10 +558,7 @@ int ratsdf_engine::free_all() {
     if (ev) (void)hipEventDestroy(ev);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
-  for (auto& ev : prof_events) {
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
+  timer.destroy();
   if (stream) (void)hipStreamDestroy(stream);
   return RATSDF_OK;
 }
@@ -592,6 +681,58 @@ int ratsdf_engine::ensure_stage(size_t npix) {
   return RATSDF_OK;
 }
 
+// (the slot stride is the ring's, not the call's: a smaller image after a larger one must land in the SAME slot
+// memory the slot's events guard -- with a per-call stride its bytes would fall inside other slots that frames of
+// earlier calls, which are not waited for, may still be reading)
+ratsdf_engine::StageSlot ratsdf_engine::stage_slot(int slot, size_t npix) const {
+  const size_t off = (size_t)slot * stage_pix * 16;
+  return StageSlot{h_stage.as<uint8_t>() + off, d_stage.as<uint8_t>() + off, npix};
+}
+
+// The caller's pageable images into the slot's page-locked memory, side by side by the copy helpers (HostCopyPool);
+// every image in `parts` pieces of about equal size.  The slot's last upload must have left that memory.
+void ratsdf_engine::stage_fill(const StageSlot& s, const void* rgb, const void* depth, const void* ht, const void* lt,
+                               int parts) {
+  HostCopyPool::Piece pieces[8];
+  int np = 0;
+  auto add = [&](size_t off, const void* src, size_t bytes) {
+    const size_t step = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
+    for (size_t o = 0; o < bytes; o += step)
+      pieces[np++] = HostCopyPool::Piece{s.h + off + o, (const uint8_t*)src + o, std::min(step, bytes - o)};
+  };
+  add(0, depth, s.npix * 4);
+  if (ht) {
+    add(s.npix * 4, ht, s.npix * 4);
+    add(s.npix * 8, lt, s.npix * 4);
+  }
+  add(s.npix * 12, rgb, s.npix * 3);
+  if (HostCopyPool* cp = host_copy_pool()) {
+    cp->copy(pieces, np);
+  } else {
+    for (int i = 0; i < np; ++i) memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes);
+  }
+}
+
+// ... and from there into its device memory: one copy with semantics, depth and rgb without (no ht, lt)
+int ratsdf_engine::stage_upload(const StageSlot& s, bool sem, hipStream_t cs) {
+  if (sem) {
+    HIPCHK(hipMemcpyAsync(s.d, s.h, s.npix * 15, hipMemcpyHostToDevice, cs));
+  } else {
+    HIPCHK(hipMemcpyAsync(s.d, s.h, s.npix * 4, hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(s.d + s.npix * 12, s.h + s.npix * 12, s.npix * 3, hipMemcpyHostToDevice, cs));
+  }
+  return RATSDF_OK;
+}
+
+// A failed host-image call: whatever happened, nothing stays queued that reads a half-prepared slot or the caller's
+// buffers.
+int ratsdf_engine::stage_fail(int status) {
+  (void)hipStreamSynchronize(copy_stream);
+  (void)hipStreamSynchronize(copy_stream2);
+  abandon_pipeline();
+  return status;
+}
+
 // A device buffer and its page-locked twin, regrown together (to `bytes`) when either holds less than `need`; the
 // stream is drained first: what it has queued may still use the old ones.
 int ratsdf_engine::grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes) {
@@ -634,10 +775,16 @@ int ratsdf_engine::alloc_rank(uint32_t nranks, unsigned par, const CandJob* next
 // After a failed launch or copy in the middle of a batch: nothing may stay queued that reads the
 // caller's buffers, and the look-ahead state must not leak into the next call (a frame that skipped
 // k_cand because "its candidate pass already ran" would consume the stale lists of a frame that
-// never came).
-void ratsdf_engine::abandon_pipeline() {
+// never came).  A group, whose launches were queued on its own stream on behalf of members that do not know about
+// them, says how many frames it launched (the last of them owes its carve tail) and has the next candidate counters
+// cleared whatever cand_ready says: its look-ahead passes are not in the members' books.
+void ratsdf_engine::abandon_pipeline(int frames_launched, bool clear_next) {
   if (stream) (void)hipStreamSynchronize(stream);
-  if (cand_ready && cand[parity].count)  // lists filled for a frame that will not be integrated
+  if (frames_launched > 0) {
+    parity = (parity + (unsigned)frames_launched) & 1u;
+    pending = true;
+  }
+  if ((cand_ready || clear_next) && cand[parity].count)  // lists filled for a frame that will not be integrated
     (void)hipMemsetAsync(cand[parity].count, 0, (size_t)kCandSegs * kCandCountStride * 4, stream);
   cand_ready = false;
   (void)settle();
@@ -691,6 +838,17 @@ FrameParams ratsdf_engine::frame_params(const FrameIn& in, int H, int W, float m
   if (P.has_sem) ever_sem = true;  // (frames are prepared in the order they are integrated)
   P.segm_live = ever_sem ? 1 : 0;
   return P;
+}
+
+// the frame's row of a job table (kernels_frame.h); `par`: the counter-set parity the frame will run with
+void ratsdf_engine::fill_job(FrameJob& j, const FrameIn& in, int H, int W, float md, unsigned par) const {
+  j.P = frame_params(in, H, W, md);
+  j.depth = (const float*)in.depth;
+  j.rgb = (const uint8_t*)in.rgb;
+  j.ht = (const float*)in.ht;
+  j.lt = (const float*)in.lt;
+  j.par = par & 1u;
+  j.pad = 0;
 }
 
 CandJob ratsdf_engine::cand_job(const FrameIn& in, const FrameParams& P, unsigned par) const {
@@ -761,6 +919,23 @@ ratsdf_engine::Geom ratsdf_engine::geometry(int H, int W, bool has_next, int spl
   return g;
 }
 
+// Where the NEXT frame's candidate pass rides, percent in k_front (interleaved A/B, profiles/r02_split_ab.txt): at
+// 640x480 10 % in k_front (20 % until round 5) and the rest at the head of k_integrate's grid (10-30 % measured the same,
+// 0 and 40 % are ~2.5 % slower: k_front is a chain of dependent round trips that a few riders do not
+// lengthen, the voxel update hides the rest); at 1280x720 all of it in k_front (best by 1-3 %, and
+// k_integrate stays the pure voxel update its roofline figure is about)
+// (k_integrate<1> runs 512-thread workgroups and hosts no look-ahead: everything in k_front then)
+int ratsdf_engine::lookahead_split(size_t npix) const {
+  if (vpl == 1) return 100;
+  return (int)(!cand_split_env && npix >= 600000 ? (unsigned)RATSDF_CAND_SPLIT_HD : cand_split);
+}
+
+// May an n-frame batch at H x W replay a captured graph (batch_graph)?  Not for the 512-thread voxel-per-lane
+// variant, not with the serial role as a launch of its own, not when a look-ahead pass is already out.
+bool ratsdf_engine::graph_eligible(int n, int H, int W) const {
+  return use_graphs && n >= 2 && !cand_ready && fused_serial && vpl != 1 && (size_t)H * W * (size_t)S < 0xFFFFFFFFull;
+}
+
 // One frame.  `next` (same image size) is the frame the caller will integrate right after this one,
 // if it already knows it: its candidate pass then rides in this frame's single-workgroup kernels.
 int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, float md) {
@@ -783,15 +958,8 @@ int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, 
 #else
   const bool inline_kernel = inline_cand;
 #endif
-  // Where the NEXT frame's candidate pass rides (interleaved A/B, profiles/r02_split_ab.txt): at
-  // 640x480 10 % in k_front (20 % until round 5) and the rest at the head of k_integrate's grid (10-30 % measured the same,
-  // 0 and 40 % are ~2.5 % slower: k_front is a chain of dependent round trips that a few riders do not
-  // lengthen, the voxel update hides the rest); at 1280x720 all of it in k_front (best by 1-3 %, and
-  // k_integrate stays the pure voxel update its roofline figure is about)
-  // (k_integrate<1> runs 512-thread workgroups and hosts no look-ahead: everything in k_front then)
-  const int split = vpl == 1 ? 100 : (int)(cand_split_env ? cand_split : (npix >= 600000 ? (unsigned)RATSDF_CAND_SPLIT_HD : cand_split));
   const int split_b = (fused_serial && vpl != 1) ? 0 : (int)(cand_split_env ? cand_split_b : 0u);
-  const Geom g = geometry(H, W, next != nullptr, split, split_b);
+  const Geom g = geometry(H, W, next != nullptr, lookahead_split(npix), split_b);
   // shares of the next frame's candidate pass: k_front, k_alloc_rank, k_integrate
   CandJob ahead_a, ahead_b, ahead_c;
   memset(&ahead_a, 0, sizeof(ahead_a));
@@ -872,20 +1040,8 @@ int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, 
   }
 #endif
 
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // (sampled: events perturb the stream; mode 2 times every frame, for latency distributions)
-  const bool timed = profiling && (prof_mode == 2 || prof_frame++ % 4 == 0);
-  if (timed) {
-    if (prof_used == prof_events.size()) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      HIPCHK(hipEventCreate(&b));
-      prof_events.emplace_back(a, b);
-    }
-    ev0 = prof_events[prof_used].first;
-    ev1 = prof_events[prof_used].second;
-    ++prof_used;
-  }
+  if (timer.on) STCHK(timer.reserve(1));
+  const auto [ev0, ev1] = timer.take();
   const unsigned integrate_grid = g.grid;
   // hipExtLaunchKernelGGL attaches the two events to the dispatch itself: their difference is the
   // kernel's own start-to-end time (what rocprofv3 reports), without the barrier packets that
@@ -925,32 +1081,7 @@ int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, 
 
   HIPCHK(hipGetLastError());
   pending = true;
-  if (profiling && prof_used >= (prof_mode == 2 ? 60000u : 4096u)) return drain_profile(false);
-  return RATSDF_OK;
-}
-
-// `final`: nothing follows the timed frames (a read-out).  An intermediate drain in mode 2 (the event pool is
-// full) keeps the LAST pair for the next drain: its period ends at the start of a frame that has not been
-// launched yet, and prof_k_us / prof_period_us must stay index-aligned (ratsdf_profile_read_frames).
-int ratsdf_engine::drain_profile(bool final) {
-  if (!prof_used) return RATSDF_OK;
-  HIPCHK(hipStreamSynchronize(stream));
-  const bool keep_last = prof_mode == 2 && !final && prof_used > 1;
-  const size_t n = keep_last ? prof_used - 1 : prof_used;
-  for (size_t i = 0; i < n; ++i) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, prof_events[i].first, prof_events[i].second));
-    prof_ms += ms;
-    ++prof_n;
-    if (prof_mode == 2) {
-      prof_k_us.push_back(ms * 1e3f);
-      float gap = 0;  // consecutive frames: start of this frame's k_integrate to the next one's (last frame: 0)
-      if (i + 1 < prof_used) HIPCHK(hipEventElapsedTime(&gap, prof_events[i].first, prof_events[i + 1].first));
-      prof_period_us.push_back(gap * 1e3f);
-    }
-  }
-  if (keep_last) std::swap(prof_events[0], prof_events[prof_used - 1]);
-  prof_used = keep_last ? 1 : 0;
+  if (timer.full()) return timer.drain(stream, false);
   return RATSDF_OK;
 }
 
@@ -999,9 +1130,88 @@ void ratsdf_engine::free_graph(BatchGraph& g) {
   g = BatchGraph();  // (and with it the job tables)
 }
 
-// The graph of an n-frame batch at H x W (built on first use, a few kept): k_cand_g for the first frame, then
-// k_front_g / k_integrate_g per frame with the look-ahead shares frame() would choose, one member (blockIdx.y = 0),
-// operands from d_eng and the graph's own job table.
+// The launches of a batch whose operands lie in device tables: n frames of S members each (blockIdx.y), engine
+// records in `engs`, frame f of member s in d_jobs[f * S + s].  k_cand_g for the first frame (nobody looked ahead
+// for it: its candidate pass runs in line), then per frame k_front_g, k_alloc_rank_g when the serial role is a launch
+// of its own (n_serial_wg == 0, diagnostic build) and k_integrate_g; `g1` is the geometry of a frame that hosts the
+// next one's look-ahead pass, `g0` of the last.  With a `timer` the k_integrate_g launches are direct ones that carry
+// its events (hipExtLaunchKernelGGL attaches them to the dispatch itself, see frame()); without, plain launches: what
+// a stream capture records.  Returns the frames enqueued completely and the status: after a refused launch the
+// caller has that many frames queued on behalf of its engines.
+struct Enqueued {
+  int frames, status;
+};
+static Enqueued enqueue_jobs(hipStream_t stream, EnginePtr engs, const FrameJob* d_jobs, int n, int S,
+                             const ratsdf_engine::Geom& g0, const ratsdf_engine::Geom& g1, uint32_t commit_rot,
+                             uint32_t n_serial_wg, [[maybe_unused]] uint32_t tail, [[maybe_unused]] int vpl,
+                             KernelTimer* timer) {
+  {
+    AheadGeom all = g0.a;
+    all.first_tile = 0;
+    all.n_tiles = g0.n_cand_wg * 4;
+    hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, S), dim3(256), 0, stream, engs, (JobPtr)d_jobs, all);
+  }
+  if (hipGetLastError() != hipSuccess) return {0, RATSDF_ERR_DEVICE};
+  for (int f = 0; f < n; ++f) {
+    const bool has_next = f + 1 < n;
+    const ratsdf_engine::Geom& gg = has_next ? g1 : g0;
+    JobPtr cur = (JobPtr)(d_jobs + (size_t)f * S);
+    JobPtr nxt = (JobPtr)(d_jobs + (size_t)(has_next ? f + 1 : f) * S);
+#ifdef RATSDF_STAMPS
+    if (tail & 1u)
+      hipLaunchKernelGGL(k_front_g<true>, dim3(gg.n_front_wg, S), dim3(256), 0, stream, engs, cur, nxt,
+                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, tail, gg.a);
+    else
+#endif
+      hipLaunchKernelGGL(k_front_g<false>, dim3(gg.n_front_wg, S), dim3(256), 0, stream, engs, cur, nxt,
+                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, 0u, gg.a);
+#ifdef RATSDF_STAMPS
+    if (!n_serial_wg) {
+      const unsigned extra_b = gg.b.n_tiles ? (gg.b.n_tiles + gg.b.tiles_per_wg - 1) / gg.b.tiles_per_wg : 0;
+      hipLaunchKernelGGL(k_alloc_rank_g, dim3(1 + extra_b, S), dim3(1024), kSerialLdsBytes, stream, engs, cur, nxt,
+                         gg.b);
+    }
+#endif
+    const unsigned extra_c = ((gg.c.n_tiles + 3) / 4 + 7u) & ~7u;  // whole groups of 8 (XCD mapping)
+    const dim3 grid(gg.grid + n_serial_wg + extra_c, S);
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    if (timer) ev = timer->take();
+#define RATSDF_LAUNCH_INTEGRATE_G(V, T, NT)                                                                    \
+  do {                                                                                                         \
+    const auto kernel = k_integrate_g<V, T>;                                                                   \
+    if (timer)                                                                                                 \
+      hipExtLaunchKernelGGL(kernel, grid, dim3(NT), 0, stream, ev.first, ev.second, 0, engs, cur, nxt,         \
+                            (uint32_t)gg.grid, n_serial_wg, (uint32_t)extra_c, commit_rot, gg.c);              \
+    else                                                                                                       \
+      hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, stream, engs, cur, nxt, (uint32_t)gg.grid, n_serial_wg,    \
+                         (uint32_t)extra_c, commit_rot, gg.c);                                                 \
+  } while (0)
+    // (the voxels-per-lane variants 1 / 4 / 8 are tuning options: without the front-tail path)
+#ifdef RATSDF_STAMPS
+    switch (vpl) {
+      case 1: RATSDF_LAUNCH_INTEGRATE_G(1, false, 512); break;
+      case 8: RATSDF_LAUNCH_INTEGRATE_G(8, false, RATSDF_INTEG_NT); break;
+      case 4: RATSDF_LAUNCH_INTEGRATE_G(4, false, RATSDF_INTEG_NT); break;
+      default:
+        if (tail & 1u) RATSDF_LAUNCH_INTEGRATE_G(2, true, RATSDF_INTEG_NT);
+        else RATSDF_LAUNCH_INTEGRATE_G(2, false, RATSDF_INTEG_NT);
+    }
+#else
+    RATSDF_LAUNCH_INTEGRATE_G(2, false, RATSDF_INTEG_NT);  // the one form the product ships
+#endif
+#undef RATSDF_LAUNCH_INTEGRATE_G
+    if (hipGetLastError() != hipSuccess) return {f, RATSDF_ERR_DEVICE};  // a launch of this frame was refused
+    if (timer && timer->full()) {
+      const int st = timer->drain(stream);
+      if (st != RATSDF_OK) return {f + 1, st};
+    }
+  }
+  return {n, RATSDF_OK};
+}
+
+// The graph of an n-frame batch at H x W (built on first use, a few kept): the launches of enqueue_jobs with the
+// look-ahead shares frame() would choose, one member (blockIdx.y = 0), operands from d_eng and the graph's own job
+// table.
 int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
   *out = nullptr;
   for (auto& g : graphs)
@@ -1040,53 +1250,13 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
     if (g.h_jobs[i].alloc((size_t)n * sizeof(FrameJob)) != RATSDF_OK ||
         hipEventCreateWithFlags(&g.ev[i], hipEventDisableTiming) != hipSuccess)
       return fail("staging allocation");
-  const size_t npix = (size_t)H * W;
-  const int split = vpl == 1 ? 100 : (int)(cand_split_env ? cand_split : (npix >= 600000 ? (unsigned)RATSDF_CAND_SPLIT_HD : cand_split));
-  const Geom g1 = geometry(H, W, true, split, 0);
+  // (graph_eligible: the serial role rides in k_integrate_g, whose first 8 extra workgroups are its own)
+  const Geom g1 = geometry(H, W, true, lookahead_split((size_t)H * W), 0);
   const Geom g0 = geometry(H, W, false, 0, 0);
-  const uint32_t n_serial_wg = 8u;
-  const uint32_t commit_rot = commit_rotation(g0.grid, g0.grid);
-  [[maybe_unused]] const uint32_t tail = (tab.tail_on ? 1u : 0u) | front_prio;
-  EnginePtr engs = (EnginePtr)d_eng;
   if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) return fail("hipStreamBeginCapture");
-  {
-    AheadGeom all = g0.a;
-    all.first_tile = 0;
-    all.n_tiles = g0.n_cand_wg * 4;
-    hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, 1), dim3(256), 0, stream, engs, (JobPtr)d_jobs, all);
-  }
-  for (int f = 0; f < n; ++f) {
-    const bool has_next = f + 1 < n;
-    const Geom& gg = has_next ? g1 : g0;
-    JobPtr cur = (JobPtr)(d_jobs + f);
-    JobPtr nxt = (JobPtr)(d_jobs + (has_next ? f + 1 : f));
-#ifdef RATSDF_STAMPS
-    if (tab.tail_on)
-      hipLaunchKernelGGL(k_front_g<true>, dim3(gg.n_front_wg, 1), dim3(256), 0, stream, engs, cur, nxt,
-                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, tail, gg.a);
-    else
-#endif
-      hipLaunchKernelGGL(k_front_g<false>, dim3(gg.n_front_wg, 1), dim3(256), 0, stream, engs, cur, nxt,
-                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, 0u, gg.a);
-    const unsigned extra_c = ((gg.c.n_tiles + 3) / 4 + 7u) & ~7u;
-#define RATSDF_GRAPH_INTEGRATE(V, T)                                                                                \
-  hipLaunchKernelGGL((k_integrate_g<V, T>), dim3(gg.grid + n_serial_wg + extra_c, 1), dim3(RATSDF_INTEG_NT), 0, stream, \
-                     engs, cur, nxt, (uint32_t)gg.grid, n_serial_wg, (uint32_t)extra_c, commit_rot, gg.c)
-#ifdef RATSDF_STAMPS
-    switch (vpl) {
-      case 8: RATSDF_GRAPH_INTEGRATE(8, false); break;
-      case 4: RATSDF_GRAPH_INTEGRATE(4, false); break;
-      default:
-        if (tab.tail_on) RATSDF_GRAPH_INTEGRATE(2, true);
-        else RATSDF_GRAPH_INTEGRATE(2, false);
-    }
-#else
-    RATSDF_GRAPH_INTEGRATE(2, false);
-#endif
-#undef RATSDF_GRAPH_INTEGRATE
-  }
-  const hipError_t launch_err = hipGetLastError();
-  if (hipStreamEndCapture(stream, &g.graph) != hipSuccess || launch_err != hipSuccess || !g.graph)
+  const Enqueued q = enqueue_jobs(stream, (EnginePtr)d_eng, d_jobs, n, 1, g0, g1, commit_rotation(g0.grid, g0.grid), 8u,
+                                  (tab.tail_on ? 1u : 0u) | front_prio, vpl, nullptr);
+  if (hipStreamEndCapture(stream, &g.graph) != hipSuccess || q.status != RATSDF_OK || !g.graph)
     return fail("capture");
   if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) return fail("hipGraphInstantiate");
   g.last_use = ++graph_clock;
@@ -1313,9 +1483,7 @@ int ratsdf_integrate_device(ratsdf_engine* e, const void* d_rgb, const void* d_d
   if (!e || !d_rgb || !d_depth || !K || !T || height <= 0 || width <= 0)
     return RATSDF_ERR_BAD_ARGUMENT;
   if (!finite_frame(*K, *T, max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
-  if (!d_ht || !d_lt) d_ht = d_lt = nullptr;
-  const ratsdf_engine::FrameIn in{d_rgb, d_depth, d_ht, d_lt, K, T};
-  return e->frame(in, nullptr, height, width, max_depth);
+  return e->frame(ratsdf_engine::FrameIn::of(d_rgb, d_depth, d_ht, d_lt, K, T), nullptr, height, width, max_depth);
 }
 
 int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_rgb,
@@ -1328,19 +1496,13 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
     return RATSDF_ERR_BAD_ARGUMENT;
   for (int i = 0; i < n; ++i)
     if (!d_rgb[i] || !d_depth[i] || !finite_frame(K[i], T[i], max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
-  auto input = [&](int i) {
-    const void* ht = (d_ht && d_lt) ? d_ht[i] : nullptr;
-    const void* lt = (d_ht && d_lt) ? d_lt[i] : nullptr;
-    if (!ht || !lt) ht = lt = nullptr;
-    return ratsdf_engine::FrameIn{d_rgb[i], d_depth[i], ht, lt, &K[i], &T[i]};
-  };
+  auto input = [&](int i) { return ratsdf_engine::FrameIn::at((size_t)i, d_rgb, d_depth, d_ht, d_lt, K, T); };
   // The captured form: one graph launch for the whole batch (not while individual launches carry profiling
-  // events, not for the 512-thread voxel-per-lane variant, not with the serial role as a launch of its own).
+  // events, nor for the shapes graph_eligible refuses).
   // (profiling, mode 1: every fourth batch is launched frame by frame and carries the events -- a sample of the
   // same stream inside the same timed region; mode 2 times every frame: no graphs)
-  const bool sampled = e->profiling && (e->prof_mode == 2 || (e->prof_batch++ & 3u) == 0);
-  if (e->use_graphs && n >= 2 && !sampled && !e->cand_ready && e->fused_serial && e->vpl != 1 &&
-      (size_t)height * width * (size_t)e->S < 0xFFFFFFFFull) {
+  const bool sampled = e->timer.on && (e->timer.mode == 2 || (e->prof_batch++ & 3u) == 0);
+  if (!sampled && e->graph_eligible(n, height, width)) {
     const size_t npix = (size_t)height * width;
     STCHK(e->ensure_image(npix, npix * (size_t)e->S));
     ratsdf_engine::BatchGraph* g = nullptr;
@@ -1348,17 +1510,7 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
       const unsigned turn = g->turn++ & 1u;
       HIPCHK(hipEventSynchronize(g->ev[turn]));  // the copy that last used this staging table is done
       FrameJob* hj = g->h_jobs[turn].as<FrameJob>();
-      for (int i = 0; i < n; ++i) {
-        const ratsdf_engine::FrameIn in = input(i);
-        FrameJob& j = hj[i];
-        j.P = e->frame_params(in, height, width, max_depth);
-        j.depth = (const float*)in.depth;
-        j.rgb = (const uint8_t*)in.rgb;
-        j.ht = (const float*)in.ht;
-        j.lt = (const float*)in.lt;
-        j.par = (e->parity + (unsigned)i) & 1u;
-        j.pad = 0;
-      }
+      for (int i = 0; i < n; ++i) e->fill_job(hj[i], input(i), height, width, max_depth, e->parity + (unsigned)i);
       if (hipMemcpyAsync(g->d_jobs.as<FrameJob>(), hj, (size_t)n * sizeof(FrameJob), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
           hipEventRecord(g->ev[turn], e->stream) != hipSuccess)
         return RATSDF_ERR_DEVICE;
@@ -1375,7 +1527,7 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
   // (mode 1 samples frames 2, 6, 10, ... of the batch, never its first: the start stamp of a dispatch that finds
   // the queue idle is taken early -- events showed 100+ us for such a frame where rocprofv3's trace of the same
   // launch shows an ordinary one, tools/event_probe.py)
-  if (e->profiling && e->prof_mode != 2 && n > 2) e->prof_frame = 2;
+  if (e->timer.on && e->timer.mode != 2 && n > 2) e->timer.frame = 2;
   for (int i = 0; i < n; ++i) {
     const ratsdf_engine::FrameIn cur = input(i);
     ratsdf_engine::FrameIn nxt{};
@@ -1400,7 +1552,7 @@ int ratsdf_prepare_device_batch(ratsdf_engine* e, int n, int height, int width) 
   const size_t npix = (size_t)height * width;
   if (npix * (size_t)e->S >= 0xFFFFFFFFull) return RATSDF_ERR_BAD_ARGUMENT;
   STCHK(e->ensure_image(npix, npix * (size_t)e->S));
-  if (e->use_graphs && n >= 2 && !e->cand_ready && e->fused_serial && e->vpl != 1) {
+  if (e->graph_eligible(n, height, width)) {
     ratsdf_engine::BatchGraph* g = nullptr;
     (void)e->batch_graph(n, height, width, &g);  // (a failed capture is remembered: such batches go frame by frame)
   }
@@ -1424,61 +1576,22 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
   // nothing here waits for the GPU unless the ring is full -- the slot's previous upload (8 calls ago) must
   // have left its host memory before it is overwritten.  (Until round 4 every call ended with a stream
   // synchronisation: 2 700 frames/s at 640x480, a third of it the single-threaded staging copy.)
-  // (the slot stride is the ring's, not this call's: a smaller image after a larger one must land in the SAME slot
-  // memory the slot's events guard -- with a per-call stride its bytes would fall inside other slots that frames of
-  // earlier calls, which are not waited for, may still be reading)
-  const size_t slot_bytes = e->stage_pix * 16;
   const int slot = (int)(e->stage_no++ % kStageSlots);
-  uint8_t* h = e->h_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
-  uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
+  const ratsdf_engine::StageSlot s = e->stage_slot(slot, npix);
   HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // (an event never recorded counts as complete)
-  HostCopyPool::Piece pieces[8];
-  int np = 0;
-  auto add = [&](size_t off, const void* src, size_t bytes, int parts) {  // `parts` pieces of ~equal size
-    const size_t step = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
-    for (size_t o = 0; o < bytes; o += step)
-      pieces[np++] = HostCopyPool::Piece{h + off + o, (const uint8_t*)src + o, std::min(step, bytes - o)};
-  };
-  if (ht) {
-    add(0, depth, npix * 4, 1);
-    add(npix * 4, ht, npix * 4, 1);
-    add(npix * 8, lt, npix * 4, 1);
-    add(npix * 12, rgb, npix * 3, 1);
-  } else {
-    add(0, depth, npix * 4, 2);
-    add(npix * 12, rgb, npix * 3, 2);
-  }
-  if (HostCopyPool* cp = e->host_copy_pool()) {
-    cp->copy(pieces, np);
-  } else {
-    for (int i = 0; i < np; ++i) memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes);
-  }
+  e->stage_fill(s, rgb, depth, ht, lt, ht ? 1 : 2);  // (a TSDF-only frame's two images in halves: four pieces either way)
   hipStream_t cs = (slot & 1) ? e->copy_stream2 : e->copy_stream;
-  // whatever happens from here on, nothing stays queued that reads a half-prepared slot
-  auto fail = [&](int status) {
-    (void)hipStreamSynchronize(e->copy_stream);
-    (void)hipStreamSynchronize(e->copy_stream2);
-    e->abandon_pipeline();
-    return status;
-  };
   // the slot's device memory was last read by the frame that used it kStageSlots frames ago (of either host-image
   // entry point): its use_ev.  Nothing else on the engine's stream reads the staging slots.
-  if (hipStreamWaitEvent(cs, e->use_ev[slot], 0) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
-  if (ht) {
-    if (hipMemcpyAsync(d, h, npix * 15, hipMemcpyHostToDevice, cs) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
-  } else {
-    if (hipMemcpyAsync(d, h, npix * 4, hipMemcpyHostToDevice, cs) != hipSuccess ||
-        hipMemcpyAsync(d + npix * 12, h + npix * 12, npix * 3, hipMemcpyHostToDevice, cs) != hipSuccess)
-      return fail(RATSDF_ERR_DEVICE);
-  }
+  if (hipStreamWaitEvent(cs, e->use_ev[slot], 0) != hipSuccess) return e->stage_fail(RATSDF_ERR_DEVICE);
+  int st = e->stage_upload(s, ht != nullptr, cs);
+  if (st != RATSDF_OK) return e->stage_fail(st);
   if (hipEventRecord(e->stage_ev[slot], cs) != hipSuccess ||
       hipStreamWaitEvent(e->stream, e->stage_ev[slot], 0) != hipSuccess)
-    return fail(RATSDF_ERR_DEVICE);
-  const ratsdf_engine::FrameIn in{d + npix * 12, d, ht ? d + npix * 4 : nullptr,
-                                  ht ? d + npix * 8 : nullptr, K, T};
-  int st = e->frame(in, nullptr, height, width, max_depth);
-  if (st != RATSDF_OK) return fail(st);
-  if (hipEventRecord(e->use_ev[slot], e->stream) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
+    return e->stage_fail(RATSDF_ERR_DEVICE);
+  st = e->frame(s.input(K, T, ht != nullptr), nullptr, height, width, max_depth);
+  if (st != RATSDF_OK) return e->stage_fail(st);
+  if (hipEventRecord(e->use_ev[slot], e->stream) != hipSuccess) return e->stage_fail(RATSDF_ERR_DEVICE);
   if (!e->sync_integrate) return RATSDF_OK;
   return e->sticky();  // cudaStreamSynchronize(stream_), voxel_tsdf.cu:450
 }
@@ -1528,7 +1641,8 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
         ++run;
     *took = run;
     hipStream_t cs = ((copy_no++ & 1) && two_streams) ? e->copy_stream2 : e->copy_stream;
-    uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
+    const ratsdf_engine::StageSlot s = e->stage_slot(slot, npix);
+    uint8_t* const d = s.d;
     // (the slot's last reader: a frame of this call or of an earlier one; an event never recorded counts as complete)
     for (int j = 0; j < run; ++j) HIPCHK(hipStreamWaitEvent(cs, e->use_ev[slot + j], 0));
     const uint8_t* h0 = reinterpret_cast<const uint8_t*>(depth[i]);
@@ -1542,44 +1656,16 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
       }
       HIPCHK(hipMemcpyAsync(d + npix * 12, rgb[i], npix * 3, hipMemcpyHostToDevice, cs));
     } else {
-      uint8_t* h = e->h_stage.as<uint8_t>() + (size_t)slot * slot_bytes;
       HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // the slot's last upload has left its page-locked memory
-      // (the frame's images side by side, by the engine's copy helpers: HostCopyPool)
-      HostCopyPool::Piece pieces[4];
-      int np = 0;
-      pieces[np++] = HostCopyPool::Piece{h, depth[i], npix * 4};
-      if (sem(i)) {
-        pieces[np++] = HostCopyPool::Piece{h + npix * 4, ht[i], npix * 4};
-        pieces[np++] = HostCopyPool::Piece{h + npix * 8, lt[i], npix * 4};
-      }
-      pieces[np++] = HostCopyPool::Piece{h + npix * 12, rgb[i], npix * 3};
-      if (HostCopyPool* cp = e->host_copy_pool()) {
-        cp->copy(pieces, np);
-      } else {
-        for (int q = 0; q < np; ++q) memcpy(pieces[q].dst, pieces[q].src, pieces[q].bytes);
-      }
-      if (sem(i)) {
-        HIPCHK(hipMemcpyAsync(d, h, npix * 15, hipMemcpyHostToDevice, cs));
-      } else {  // depth | (no ht, lt) | rgb
-        HIPCHK(hipMemcpyAsync(d, h, npix * 4, hipMemcpyHostToDevice, cs));
-        HIPCHK(hipMemcpyAsync(d + npix * 12, h + npix * 12, npix * 3, hipMemcpyHostToDevice, cs));
-      }
+      e->stage_fill(s, rgb[i], depth[i], sem(i) ? ht[i] : nullptr, sem(i) ? lt[i] : nullptr, 1);
+      STCHK(e->stage_upload(s, sem(i), cs));
     }
     for (int j = 0; j < run; ++j) HIPCHK(hipEventRecord(e->stage_ev[slot + j], cs));
     return RATSDF_OK;
   };
-  auto input = [&](int i) {
-    uint8_t* d = e->d_stage.as<uint8_t>() + (size_t)slot_of(i) * slot_bytes;
-    return ratsdf_engine::FrameIn{d + npix * 12, d, sem(i) ? d + npix * 4 : nullptr,
-                                  sem(i) ? d + npix * 8 : nullptr, &K[i], &T[i]};
-  };
+  auto input = [&](int i) { return e->stage_slot(slot_of(i), npix).input(&K[i], &T[i], sem(i)); };
   // whatever happens, the caller's buffers (and the staging slots) are no longer in use on return
-  auto fail = [&](int status) {
-    (void)hipStreamSynchronize(e->copy_stream);
-    (void)hipStreamSynchronize(e->copy_stream2);
-    e->abandon_pipeline();
-    return status;
-  };
+  auto fail = [&](int status) { return e->stage_fail(status); };
   // (No fence against earlier calls: frames of earlier host-image calls that are still in flight are what the
   // slots' events stand for, and nothing else on the engine's stream touches the staging slots.  Until round 5
   // every call began by making both copy streams wait for ALL earlier work of the engine's stream and ended with
@@ -1750,11 +1836,12 @@ int ratsdf_profile_enable(ratsdf_engine* e, int enable) {
   DeviceGuard guard(e ? e->device : -1);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
   if (!e) return RATSDF_ERR_BAD_ARGUMENT;
-  const int st = e->drain_profile();
-  e->profiling = enable != 0;
-  e->prof_mode = enable == 2 ? 2 : 1;
-  e->prof_k_us.clear();
-  e->prof_period_us.clear();
+  KernelTimer& t = e->timer;
+  const int st = t.drain(e->stream);
+  t.on = enable != 0;
+  t.mode = enable == 2 ? 2 : 1;
+  t.k_us.clear();
+  t.period_us.clear();
   return st;
 }
 
@@ -1762,17 +1849,16 @@ int ratsdf_profile_read_frames(ratsdf_engine* e, float* k_us, float* period_us, 
   DeviceGuard guard(e ? e->device : -1);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
   if (!e || !n || capacity < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  const int st = e->drain_profile();
-  const int have = (int)e->prof_k_us.size();
+  KernelTimer& t = e->timer;
+  const int st = t.read(e->stream, nullptr, nullptr);
+  const int have = (int)t.k_us.size();
   *n = have;
   for (int i = 0; i < have && i < capacity; ++i) {
-    if (k_us) k_us[i] = e->prof_k_us[(size_t)i];
-    if (period_us) period_us[i] = (size_t)i < e->prof_period_us.size() ? e->prof_period_us[(size_t)i] : 0.f;
+    if (k_us) k_us[i] = t.k_us[(size_t)i];
+    if (period_us) period_us[i] = (size_t)i < t.period_us.size() ? t.period_us[(size_t)i] : 0.f;
   }
-  e->prof_k_us.clear();
-  e->prof_period_us.clear();
-  e->prof_ms = 0;
-  e->prof_n = 0;
+  t.k_us.clear();
+  t.period_us.clear();
   return st;
 }
 
@@ -1780,12 +1866,7 @@ int ratsdf_profile_read(ratsdf_engine* e, double* ms, int64_t* launches) {
   DeviceGuard guard(e ? e->device : -1);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
   if (!e) return RATSDF_ERR_BAD_ARGUMENT;
-  const int st = e->drain_profile();
-  if (ms) *ms = e->prof_ms;
-  if (launches) *launches = e->prof_n;
-  e->prof_ms = 0;
-  e->prof_n = 0;
-  return st;
+  return e->timer.read(e->stream, ms, launches);
 }
 
 int ratsdf_num_active_blocks(ratsdf_engine* e, int32_t* out) {
@@ -2857,25 +2938,8 @@ struct ratsdf_group {
   hipEvent_t ev_stage[2] = {nullptr, nullptr};
   unsigned batch_no = 0;
   int split_a = 100, split_b = 0;  // look-ahead share of k_front / k_alloc_rank (rest: k_integrate)
-  bool profiling = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-  size_t prof_used = 0;
-  uint64_t prof_frame = 0;
-  double prof_ms = 0;
-  int64_t prof_n = 0;
+  KernelTimer timer;  // (mode 1: every fourth frame)
 
-  int drain_profile() {
-    if (!prof_used) return RATSDF_OK;
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t i = 0; i < prof_used; ++i) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, prof_events[i].first, prof_events[i].second));
-      prof_ms += ms;
-      ++prof_n;
-    }
-    prof_used = 0;
-    return RATSDF_OK;
-  }
   void free_all() {
     if (stream) (void)hipStreamSynchronize(stream);
     for (DevMem* m : {&d_engs, &d_jobs}) m->reset();
@@ -2887,10 +2951,7 @@ struct ratsdf_group {
     for (auto& ev : ev_member)
       if (ev) (void)hipEventDestroy(ev);
     if (ev_done) (void)hipEventDestroy(ev_done);
-    for (auto& ev : prof_events) {
-      (void)hipEventDestroy(ev.first);
-      (void)hipEventDestroy(ev.second);
-    }
+    timer.destroy();
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -3007,19 +3068,9 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   for (int f = 0; f < n; ++f)
     for (int s = 0; s < S; ++s) {
       const size_t i = (size_t)f * S + s;
-      ratsdf_engine* e = g->eng[(size_t)s];
-      const void* ht = (d_ht && d_lt) ? d_ht[i] : nullptr;
-      const void* lt = (d_ht && d_lt) ? d_lt[i] : nullptr;
-      if (!ht || !lt) ht = lt = nullptr;
-      const ratsdf_engine::FrameIn in{d_rgb[i], d_depth[i], ht, lt, &K[i], &T[i]};
-      FrameJob& j = hj[i];
-      j.P = e->frame_params(in, height, width, max_depth);
-      j.depth = (const float*)in.depth;
-      j.rgb = (const uint8_t*)in.rgb;
-      j.ht = (const float*)in.ht;
-      j.lt = (const float*)in.lt;
-      j.par = (e->parity + (unsigned)f) & 1u;
-      j.pad = 0;
+      const ratsdf_engine* e = g->eng[(size_t)s];
+      e->fill_job(hj[i], ratsdf_engine::FrameIn::at(i, d_rgb, d_depth, d_ht, d_lt, K, T), height, width, max_depth,
+                  e->parity + (unsigned)f);
     }
   // ---- ordering with the members' own streams (queries, single-engine frames) ----
   for (int s = 0; s < S; ++s) {
@@ -3032,9 +3083,7 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   HIPCHK(hipEventRecord(g->ev_stage[slot], g->stream));
 
   // ---- launches ----
-  EnginePtr engs = (EnginePtr)d_engs;
   const bool fused = e0->fused_serial && e0->vpl != 1;
-  const uint32_t n_serial_wg = fused ? 8u : 0u;
   ratsdf_engine::Geom g1 = e0->geometry(height, width, true, e0->vpl == 1 ? 100 : g->split_a,
                                         (fused || e0->vpl == 1) ? 0 : g->split_b);
   ratsdf_engine::Geom g0 = e0->geometry(height, width, false, 0, 0);
@@ -3045,102 +3094,19 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   if (!e0->grid_from_env && S >= 2 && g0.grid == 4096u) g0.grid = g1.grid = 1536u;
   const unsigned grid0 = g0.grid;
   const uint32_t commit_rot = fused ? e0->commit_rotation(grid0, grid0 * (unsigned)S) : 0u;
-  {  // nobody looked ahead for the first frame: its candidate pass runs in line
-    AheadGeom all = g0.a;
-    all.first_tile = 0;
-    all.n_tiles = g0.n_cand_wg * 4;
-    hipLaunchKernelGGL(k_cand_g, dim3(g0.n_cand_wg, S), dim3(256), 0, g->stream, engs,
-                       (JobPtr)d_jobs, all);
-  }
+  // events for every frame that will be timed: created before anything is launched
+  if (g->timer.on) STCHK(g->timer.reserve((size_t)n / 4 + 2));
   // A failure from here on leaves launches queued on the group's stream on behalf of members that do
-  // not know about them: the members are brought to a consistent state before the error is returned
-  // (the counterpart of ratsdf_engine::abandon_pipeline for a group).
+  // not know about them: the members are brought to a consistent state before the error is returned.
   auto abandon = [&](int frames_launched) {
     (void)hipStreamSynchronize(g->stream);
-    for (ratsdf_engine* e : g->eng) {
-      if (frames_launched > 0) {
-        e->parity = (e->parity + (unsigned)frames_launched) & 1u;
-        e->pending = true;   // the last launched frame owes its carve tail
-      }
-      // the look-ahead pass of a frame that will not come may have filled the next candidate lists
-      if (e->cand[e->parity].count)
-        (void)hipMemsetAsync(e->cand[e->parity].count, 0, (size_t)kCandSegs * kCandCountStride * 4, e->stream);
-      e->cand_ready = false;
-      (void)e->settle();
-      (void)hipStreamSynchronize(e->stream);
-    }
+    for (ratsdf_engine* e : g->eng) e->abandon_pipeline(frames_launched, true);
   };
-  if (g->profiling) {  // events for every frame that will be timed, created before anything is launched
-    const size_t need = g->prof_used + (size_t)n / 4 + 2;
-    while (g->prof_events.size() < need) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        return RATSDF_ERR_DEVICE;
-      }
-      g->prof_events.emplace_back(a, b);
-    }
-  }
-  if (hipGetLastError() != hipSuccess) {  // k_cand_g
-    abandon(0);
-    return RATSDF_ERR_DEVICE;
-  }
-  for (int f = 0; f < n; ++f) {
-    const bool has_next = f + 1 < n;
-    const ratsdf_engine::Geom& gg = has_next ? g1 : g0;
-    JobPtr cur = (JobPtr)(d_jobs + (size_t)f * S);
-    JobPtr nxt = (JobPtr)(d_jobs + (size_t)(has_next ? f + 1 : f) * S);
-#ifdef RATSDF_STAMPS
-    if (e0->tab.tail_on)
-      hipLaunchKernelGGL(k_front_g<true>, dim3(gg.n_front_wg, S), dim3(256), 0, g->stream, engs, cur, nxt,
-                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, 1u | e0->front_prio, gg.a);
-    else
-#endif
-      hipLaunchKernelGGL(k_front_g<false>, dim3(gg.n_front_wg, S), dim3(256), 0, g->stream, engs, cur, nxt,
-                         (uint32_t)gg.n_vis_wg, (uint32_t)gg.parts, 0u, gg.a);
-#ifdef RATSDF_STAMPS
-    if (!fused) {
-      const unsigned extra_b = gg.b.n_tiles ? (gg.b.n_tiles + gg.b.tiles_per_wg - 1) / gg.b.tiles_per_wg : 0;
-      hipLaunchKernelGGL(k_alloc_rank_g, dim3(1 + extra_b, S), dim3(1024), kSerialLdsBytes, g->stream,
-                         engs, cur, nxt, gg.b);
-    }
-#endif
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g->profiling && (g->prof_frame++ % 4 == 0) && g->prof_used < g->prof_events.size()) {
-      ev0 = g->prof_events[g->prof_used].first;
-      ev1 = g->prof_events[g->prof_used].second;
-      ++g->prof_used;
-    }
-    const unsigned extra_c = ((gg.c.n_tiles + 3) / 4 + 7u) & ~7u;
-#define RATSDF_LAUNCH_INTEGRATE_G(V, T, NT)                                                            \
-  hipExtLaunchKernelGGL((k_integrate_g<V, T>), dim3(gg.grid + n_serial_wg + extra_c, S), dim3(NT), 0,  \
-                        g->stream, ev0, ev1, 0, engs, cur, nxt, (uint32_t)gg.grid, n_serial_wg,        \
-                        (uint32_t)extra_c, commit_rot, gg.c)
-#ifdef RATSDF_STAMPS
-    switch (e0->vpl) {
-      case 1: RATSDF_LAUNCH_INTEGRATE_G(1, false, 512); break;
-      case 8: RATSDF_LAUNCH_INTEGRATE_G(8, false, RATSDF_INTEG_NT); break;
-      case 4: RATSDF_LAUNCH_INTEGRATE_G(4, false, RATSDF_INTEG_NT); break;
-      default:
-        if (e0->tab.tail_on) RATSDF_LAUNCH_INTEGRATE_G(2, true, RATSDF_INTEG_NT);
-        else RATSDF_LAUNCH_INTEGRATE_G(2, false, RATSDF_INTEG_NT);
-    }
-#else
-    RATSDF_LAUNCH_INTEGRATE_G(2, false, RATSDF_INTEG_NT);
-#endif
-#undef RATSDF_LAUNCH_INTEGRATE_G
-    if (hipGetLastError() != hipSuccess) {  // a launch of this frame was refused
-      abandon(f);
-      return RATSDF_ERR_DEVICE;
-    }
-    if (g->profiling && g->prof_used >= 4096) {
-      const int st = g->drain_profile();
-      if (st != RATSDF_OK) {
-        abandon(f + 1);
-        return st;
-      }
-    }
+  const Enqueued q = enqueue_jobs(g->stream, (EnginePtr)d_engs, d_jobs, n, S, g0, g1, commit_rot, fused ? 8u : 0u,
+                                  (e0->tab.tail_on ? 1u : 0u) | e0->front_prio, e0->vpl, &g->timer);
+  if (q.status != RATSDF_OK) {
+    abandon(q.frames);
+    return q.status;
   }
   if (hipEventRecord(g->ev_done, g->stream) != hipSuccess) {
     abandon(n);
@@ -3174,8 +3140,8 @@ int ratsdf_group_profile_enable(ratsdf_group* g, int enable) {
   if (!g) return RATSDF_ERR_BAD_ARGUMENT;
   DeviceGuard guard(g->device);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  const int st = g->drain_profile();
-  g->profiling = enable != 0;
+  const int st = g->timer.drain(g->stream);
+  g->timer.on = enable != 0;
   return st;
 }
 
@@ -3183,12 +3149,7 @@ int ratsdf_group_profile_read(ratsdf_group* g, double* ms, int64_t* launches) {
   if (!g) return RATSDF_ERR_BAD_ARGUMENT;
   DeviceGuard guard(g->device);
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  const int st = g->drain_profile();
-  if (ms) *ms = g->prof_ms;
-  if (launches) *launches = g->prof_n;
-  g->prof_ms = 0;
-  g->prof_n = 0;
-  return st;
+  return g->timer.read(g->stream, ms, launches);
 }
 
 }  // extern "C"
