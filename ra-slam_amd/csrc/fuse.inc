@@ -86,12 +86,8 @@ static int fuse_chunk(ratsdf_engine* e, const FuseScratch& s, int32_t n, const i
     const uint32_t par = e->parity;  // an allocation pass of its own in the next frame's counters
     hipLaunchKernelGGL(k_fuse_alloc, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, P, d_pos, n, s.done, e->req,
                        e->req_cap, e->slow, kSlowCap, e->ctl, par);
-    st = e->alloc_rank(kFuseChunk, par);
+    st = e->commit_pass(kFuseChunk, par);
     if (st != RATSDF_OK) break;
-    hipLaunchKernelGGL(k_commit_only, dim3(256), dim3(256), 0, e->stream, e->tab, e->pool, e->req, e->req_cap,
-                       e->req_k, e->win_ranks, e->ctl, par);
-    hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par), e->ctl, par,
-                       (ratsdf_frame_stats*)nullptr);
     if (hipMemsetAsync(&s.cnt->missing, 0, 4, e->stream) != hipSuccess) {
       st = RATSDF_ERR_DEVICE;
       break;
@@ -154,11 +150,8 @@ extern "C" {
 long long ratsdf_debug_fuse_passes(void) { return acc_passes.load(); }
 
 int ratsdf_fuse_map(ratsdf_engine* dst, ratsdf_engine* src, ratsdf_fuse_stats* stats) {
-  if (!dst || !src || dst == src || dst->device != src->device || memcmp(&dst->vs, &src->vs, 4) != 0 ||
-      memcmp(&dst->trunc, &src->trunc, 4) != 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(dst->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  ENTRY(dst, src && dst != src && dst->device == src->device && memcmp(&dst->vs, &src->vs, 4) == 0 &&
+                 memcmp(&dst->trunc, &src->trunc, 4) == 0);
   ratsdf_fuse_stats acc;
   memset(&acc, 0, sizeof(acc));
   if (stats) *stats = acc;
@@ -193,10 +186,7 @@ int ratsdf_fuse_map(ratsdf_engine* dst, ratsdf_engine* src, ratsdf_fuse_stats* s
 
 int ratsdf_fuse_blocks_device(ratsdf_engine* e, int32_t n, const void* d_block_pos, const void* d_voxels,
                               ratsdf_fuse_stats* stats) {
-  if (!e || n < 0 || (n > 0 && (!d_block_pos || !d_voxels)) || ((uintptr_t)d_voxels & 15u) != 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(e->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  ENTRY(e, n >= 0 && (n == 0 || (d_block_pos && d_voxels)) && ((uintptr_t)d_voxels & 15u) == 0);
   ratsdf_fuse_stats acc;
   memset(&acc, 0, sizeof(acc));
   if (stats) *stats = acc;
@@ -213,10 +203,7 @@ int ratsdf_fuse_blocks_device(ratsdf_engine* e, int32_t n, const void* d_block_p
 
 int ratsdf_fuse_blocks(ratsdf_engine* e, int32_t n, const int16_t* bp, const float* tsdf, const ratsdf_rgbw* rgbw,
                        const float* prob, ratsdf_fuse_stats* stats) {
-  if (!e || n < 0 || (n > 0 && (!bp || !tsdf || !rgbw || !prob))) return RATSDF_ERR_BAD_ARGUMENT;
-  if (!fuse_positions_distinct(bp, (size_t)n)) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(e->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
+  ENTRY(e, n >= 0 && (n == 0 || (bp && tsdf && rgbw && prob)) && fuse_positions_distinct(bp, (size_t)n));
   ratsdf_fuse_stats acc;
   memset(&acc, 0, sizeof(acc));
   if (stats) *stats = acc;
@@ -229,6 +216,7 @@ int ratsdf_fuse_blocks(ratsdf_engine* e, int32_t n, const int16_t* bp, const flo
   STCHK(fuse_begin(e, &s, &free_before));
   // the three host arrays go up in chunks of kMapChunk blocks: {tsdf | rgbw | prob} of the chunk side by side
   DevMem stage;
+  StreamDrain drain{e->stream};
   STCHK(stage.alloc((size_t)kMapChunk * kMapRecordBytes));
   uint8_t* d = stage.as<uint8_t>();
   int st = RATSDF_OK;
@@ -248,7 +236,6 @@ int ratsdf_fuse_blocks(ratsdf_engine* e, int32_t n, const int16_t* bp, const flo
     st = fuse_chunk(e, s, m, s.pos, nullptr, (const uint32_t*)d, (const uint32_t*)(d + per),
                     (const uint32_t*)(d + 2 * per), 512u, &acc);
   }
-  (void)hipStreamSynchronize(e->stream);  // (nothing queued may outlive the staging buffer)
   return fuse_end(e, st, free_before, &acc, stats);
 }
 
@@ -269,7 +256,7 @@ int ratsdf_fuse_map_file(ratsdf_engine* e, const char* path, ratsdf_fuse_stats* 
   const int32_t n = (int32_t)m.h.n_blocks;
   // (the checkpoint reader checks entry and pool indices, not that a position sits in one live entry only)
   if (!fuse_positions_distinct(pos.data(), (size_t)n)) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(e->device);
+  DeviceGuard guard(e->device);  // (not ENTRY: the file is read and checked first, see above)
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
   ratsdf_fuse_stats acc;
   memset(&acc, 0, sizeof(acc));
@@ -285,6 +272,7 @@ int ratsdf_fuse_map_file(ratsdf_engine* e, const char* path, ratsdf_fuse_stats* 
   // pair is free again when the next chunk is read)
   HostMem host;
   DevMem dev;
+  StreamDrain drain{e->stream};
   STCHK(host.alloc((size_t)kMapChunk * kMapRecordBytes));
   STCHK(dev.alloc((size_t)kMapChunk * kMapRecordBytes));
   int st = RATSDF_OK;
@@ -302,7 +290,6 @@ int ratsdf_fuse_map_file(ratsdf_engine* e, const char* path, ratsdf_fuse_stats* 
     }
     st = fuse_records(e, s, c, s.pos, dev.as<uint32_t>(), &acc);
   }
-  (void)hipStreamSynchronize(e->stream);  // (nothing queued may outlive the staging buffers)
   return fuse_end(e, st, free_before, &acc, stats);
 }
 

@@ -305,8 +305,7 @@ extern "C" {
 
 int ratsdf_map_file_info(const char* path, ratsdf_config* cfg, int64_t* n_blocks) {
   MapContents m;
-  const int st = map_read_validate(path, nullptr, &m, nullptr);
-  if (st != RATSDF_OK) return st;
+  STCHK(map_read_validate(path, nullptr, &m, nullptr));
   if (cfg) {
     memset(cfg, 0, sizeof(*cfg));
     cfg->voxel_size = m.h.voxel_size;
@@ -322,15 +321,13 @@ int ratsdf_map_file_info(const char* path, ratsdf_config* cfg, int64_t* n_blocks
 }
 
 int ratsdf_save_map(ratsdf_engine* e, const char* path) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !path || !*path) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  { const int st0 = e->sticky(); if (st0 != RATSDF_OK) return st0; }  // (waits for the stream)
+  ENTRY(e, path && *path);
+  STCHK(e->settle());
+  STCHK(e->sticky());  // (waits for the stream)
   // the stored entries in entry order, the free list and its two counters
-  { const int st0 = e->select(kSelStored, GridBounds{}, &e->ctl->n_sel); if (st0 != RATSDF_OK) return st0; }
+  STCHK(e->select(kSelStored, GridBounds{}, &e->ctl->n_sel));
   int32_t c[4] = {0, 0, 0, 0};  // num_free | error | n_sel | free_low
-  { const int rs = e->read_small(c, &e->ctl->num_free, sizeof(c)); if (rs != RATSDF_OK) return rs; }
+  STCHK(e->read_small(c, &e->ctl->num_free, sizeof(c)));
   const uint32_t n_sel = (uint32_t)c[2];
   if (n_sel > e->vis_cap) return RATSDF_ERR_CAPACITY;
   std::vector<VisItem> items(n_sel);
@@ -437,13 +434,11 @@ int ratsdf_save_map(ratsdf_engine* e, const char* path) {
 }
 
 int ratsdf_load_map(ratsdf_engine* e, const char* path) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !path) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, path);
   MapContents m;
   FILE* f = nullptr;
   const MapHeader want = engine_header(e);
-  { const int st0 = map_read_validate(path, &want, &m, &f); if (st0 != RATSDF_OK) return st0; }
+  STCHK(map_read_validate(path, &want, &m, &f));
   FileCloser fc{f};
   // the file is good: everything the engine has enqueued finishes, then the map is replaced
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -454,6 +449,7 @@ int ratsdf_load_map(ratsdf_engine* e, const char* path) {
   int st = RATSDF_OK;
   MapStaging sg;
   DevMem entries_mem;
+  StreamDrain drain{e->stream};
   do {
     if (sg.init(m.pool_idx, e->stream) != RATSDF_OK) { st = RATSDF_ERR_DEVICE; break; }
     hipLaunchKernelGGL(k_init_table, dim3((t.num_entry + 255) / 256), dim3(256), 0, e->stream, t.entries, t.claim,
@@ -505,12 +501,7 @@ int ratsdf_load_map(ratsdf_engine* e, const char* path) {
     // occupancy bits, Table::active, claims, counters, the delta log's overflow mark, the error: as ratsdf_recover
     st = rebuild_derived(e, true);
   } while (false);
-  if (entries_mem) {
-    (void)hipStreamSynchronize(e->stream);
-    entries_mem.reset();
-  }
   if (st != RATSDF_OK) {
-    (void)hipStreamSynchronize(e->stream);
     (void)map_reset_empty(e);
     return st;
   }

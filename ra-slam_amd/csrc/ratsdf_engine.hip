@@ -129,6 +129,22 @@ constexpr int kUploadRun = 4;    // frames that go up with one copy when they li
 
 }  // namespace
 
+// The head of an entry point, in the order that is contract: the engine's (or group's) device made current for the
+// call, RATSDF_ERR_DEVICE if it cannot be; then RATSDF_ERR_BAD_ARGUMENT for a null handle or when `args_ok` -- read
+// only with a handle -- does not hold.  An entry point that needs the last frame's carve pass completed says
+// STCHK(e->settle()) next.
+#define ENTRY(h, args_ok)                             \
+  DeviceGuard guard((h) ? (h)->device : -1);          \
+  if (!guard.ok()) return RATSDF_ERR_DEVICE;          \
+  if (!(h) || !(args_ok)) return RATSDF_ERR_BAD_ARGUMENT
+
+// Nothing queued may outlive a function's local buffers (hip_mem.h: the owner never synchronises).  Declared AFTER
+// them, it drains the stream before they are freed, on every way out.
+struct StreamDrain {
+  hipStream_t stream;
+  ~StreamDrain() { (void)hipStreamSynchronize(stream); }
+};
+
 // Staging copies of the host-image entry points (caller's pageable images -> the engine's page-locked slot):
 // a 640x480 frame is 4.6 MB, which one core copies at ~10 GB/s -- 2 200 frames/s before anything else
 // happens.  The images of a frame are copied side by side by a few helper threads (started on first use,
@@ -469,6 +485,7 @@ struct ratsdf_engine : EngineMem {
   int upload_record();
   RankBufs rank_bufs(uint32_t nranks) const;
   int alloc_rank(uint32_t nranks, unsigned par, const CandJob* next = nullptr, bool frame = false);
+  int commit_pass(uint32_t nranks, unsigned par);
   int settle();
   void abandon_pipeline(int frames_launched = 0, bool clear_next = false);
   CarveBufs carve_bufs(unsigned par) const;
@@ -744,8 +761,6 @@ int ratsdf_engine::grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes) {
   return h.alloc(bytes);
 }
 
-// rank kernel (resolve + mark + scan) on a rank space of `nranks`; the commit itself happens inside
-// k_integrate for frames and in k_commit_only for the stand-alone test hook
 CarveBufs ratsdf_engine::carve_bufs(unsigned par) const {
   CarveBufs cb;
   cb.del = del_list[par & 1u];
@@ -759,6 +774,8 @@ CarveBufs ratsdf_engine::carve_bufs(unsigned par) const {
   return cb;
 }
 
+// rank kernel (resolve + mark + scan) on a rank space of `nranks`; the commit itself happens inside
+// k_integrate for frames and in commit_pass's k_commit_only otherwise
 int ratsdf_engine::alloc_rank(uint32_t nranks, unsigned par, const CandJob* next, bool frame) {
   CandJob none;
   memset(&none, 0, sizeof(none));
@@ -769,6 +786,18 @@ int ratsdf_engine::alloc_rank(uint32_t nranks, unsigned par, const CandJob* next
                      serial_lds, stream, tab, pool, rb, carve_bufs(par ^ 1u), ctl,
                      (uint32_t)par, d_stats, frame ? cand[par].count : (uint32_t*)nullptr, job);
   HIPCHK(hipGetLastError());
+  return RATSDF_OK;
+}
+
+// An allocation pass of its own, outside a frame, over the request list a kernel has just filled in the counters of
+// parity `par`: the rank kernel, the commits, and k_settle -- no deletes in such a pass, it just zeroes the counters
+// again.  After a refused rank launch nothing further is launched.
+int ratsdf_engine::commit_pass(uint32_t nranks, unsigned par) {
+  STCHK(alloc_rank(nranks, par));
+  hipLaunchKernelGGL(k_commit_only, dim3(256), dim3(256), 0, stream, tab, pool, req, req_cap, req_k, win_ranks, ctl,
+                     (uint32_t)par);
+  hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, stream, tab, pool, carve_bufs(par), ctl, (uint32_t)par,
+                     (ratsdf_frame_stats*)nullptr);
   return RATSDF_OK;
 }
 
@@ -1265,6 +1294,27 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
   return RATSDF_OK;
 }
 
+// a sticky error some finished launch has already raised, without waiting for the stream (ratsdf_engine::sticky): the
+// check of the asynchronous entry points of sample.inc and esdf.inc
+static int sticky_raised(ratsdf_engine* e) {
+  return *(volatile uint32_t*)e->h_err != 0u ? e->sticky() : RATSDF_OK;
+}
+
+// exclusive positions of the set items of a 0/1 mask (device arrays), and in *h_total their number; waits for the stream
+// (rebuild_derived's free list, the mesh gather of query.inc)
+static int mask_positions(ratsdf_engine* e, const uint32_t* mask, size_t n, uint32_t* pos,
+                          uint32_t* scratch_tiles, uint32_t* d_total, uint32_t* h_total) {
+  const uint32_t ntiles = (uint32_t)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(k_mask_tile_sums, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, scratch_tiles, ntiles,
+                     d_total);
+  hipLaunchKernelGGL(k_mask_positions, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles,
+                     pos);
+  HIPCHK(hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return RATSDF_OK;
+}
+
 // ================================== C ABI =====================================================
 extern "C" {
 
@@ -1279,7 +1329,7 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RATSDF_ERR_NO_DEVICE;
   if (cfg->device < 0 || cfg->device >= ndev) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(cfg->device);  // the caller's current device is restored on return
+  DeviceGuard guard(cfg->device);  // (not ENTRY: there is no engine yet, the device comes from the configuration)
   if (!guard.ok()) return RATSDF_ERR_DEVICE;
   ratsdf_engine* e = new (std::nothrow) ratsdf_engine();
   if (!e) return RATSDF_ERR_DEVICE;
@@ -1467,9 +1517,7 @@ int ratsdf_create(float voxel_size, float truncation, int device, ratsdf_engine*
 }
 
 int ratsdf_destroy(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   e->free_all();
   delete e;
   return RATSDF_OK;
@@ -1478,10 +1526,7 @@ int ratsdf_destroy(ratsdf_engine* e) {
 int ratsdf_integrate_device(ratsdf_engine* e, const void* d_rgb, const void* d_depth,
                             const void* d_ht, const void* d_lt, int height, int width,
                             float max_depth, const ratsdf_intrinsics* K, const ratsdf_pose* T) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !d_rgb || !d_depth || !K || !T || height <= 0 || width <= 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, d_rgb && d_depth && K && T && height > 0 && width > 0);
   if (!finite_frame(*K, *T, max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   return e->frame(ratsdf_engine::FrameIn::of(d_rgb, d_depth, d_ht, d_lt, K, T), nullptr, height, width, max_depth);
 }
@@ -1490,10 +1535,7 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
                                   const void* const* d_depth, const void* const* d_ht,
                                   const void* const* d_lt, int height, int width, float max_depth,
                                   const ratsdf_intrinsics* K, const ratsdf_pose* T) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || (n > 0 && (!d_rgb || !d_depth || !K || !T)) || height <= 0 || width <= 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, n >= 0 && (n == 0 || (d_rgb && d_depth && K && T)) && height > 0 && width > 0);
   for (int i = 0; i < n; ++i)
     if (!d_rgb[i] || !d_depth[i] || !finite_frame(K[i], T[i], max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   auto input = [&](int i) { return ratsdf_engine::FrameIn::at((size_t)i, d_rgb, d_depth, d_ht, d_lt, K, T); };
@@ -1546,9 +1588,7 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
 // and instantiation inside its first batch.  Nothing is launched; a shape the engine launches frame by frame
 // anyway (n < 2, graphs off) only gets its scratch.
 int ratsdf_prepare_device_batch(ratsdf_engine* e, int n, int height, int width) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || height <= 0 || width <= 0) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, n >= 0 && height > 0 && width > 0);
   const size_t npix = (size_t)height * width;
   if (npix * (size_t)e->S >= 0xFFFFFFFFull) return RATSDF_ERR_BAD_ARGUMENT;
   STCHK(e->ensure_image(npix, npix * (size_t)e->S));
@@ -1562,10 +1602,7 @@ int ratsdf_prepare_device_batch(ratsdf_engine* e, int n, int height, int width) 
 int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, const float* ht,
                      const float* lt, int height, int width, float max_depth,
                      const ratsdf_intrinsics* K, const ratsdf_pose* T) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !rgb || !depth || !K || !T || height <= 0 || width <= 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, rgb && depth && K && T && height > 0 && width > 0);
   if (!finite_frame(*K, *T, max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   if (!ht || !lt) ht = lt = nullptr;  // modules/tsdf_module.cc:27-31
   const size_t npix = (size_t)height * width;
@@ -1600,10 +1637,7 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
                            const float* const* depth, const float* const* ht,
                            const float* const* lt, int height, int width, float max_depth,
                            const ratsdf_intrinsics* K, const ratsdf_pose* T, int pinned) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || (n > 0 && (!rgb || !depth || !K || !T)) || height <= 0 || width <= 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, n >= 0 && (n == 0 || (rgb && depth && K && T)) && height > 0 && width > 0);
   for (int i = 0; i < n; ++i)
     if (!rgb[i] || !depth[i] || !finite_frame(K[i], T[i], max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   if (n == 0) return e->sticky();
@@ -1733,9 +1767,7 @@ int ratsdf_host_free(void* p) {
 }
 
 int ratsdf_synchronize(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   // (no k_settle here: what the last frame's carve pass still owes -- pool releases, its statistics -- is done by the
   // next frame's launches, or by the entry point that reads the map, the free list or the statistics: each of them
   // settles first.  A caller that synchronises after every frame, TSDFGrid::Integrate's convention, paid a fourth
@@ -1743,8 +1775,6 @@ int ratsdf_synchronize(ratsdf_engine* e) {
   return e->sticky();
 }
 
-static int mask_positions(ratsdf_engine* e, const uint32_t* mask, size_t n, uint32_t* pos, uint32_t* scratch_tiles,
-                          uint32_t* d_total, uint32_t* h_total);
 
 // After a sticky error (RATSDF_ERR_TIMEOUT above all: a workgroup gave up waiting and skipped its share of a frame) the
 // map is what the frames before left plus a part of the failed one, and the structures DERIVED from the directory no
@@ -1768,49 +1798,44 @@ static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   DevMem tmp;  // unused flags | positions | tile sums | total
   STCHK(tmp.alloc((2 * nb + ntiles + 2) * 4));
   uint32_t *unused = tmp.as<uint32_t>(), *pos = unused + nb, *tiles = pos + nb, *d_total = tiles + ntiles + 1;
-  auto fail = [&](int st) {  // (nothing queued may outlive `tmp`)
-    (void)hipStreamSynchronize(e->stream);
-    return st;
-  };
-#define REC_CHK(expr) do { if ((expr) != hipSuccess) return fail(RATSDF_ERR_DEVICE); } while (0)
-  REC_CHK(hipMemsetAsync(t.occ, 0, (size_t)occ_words * 8, e->stream));
-  REC_CHK(hipMemsetAsync(t.active, 0xFF, nb * sizeof(VisItem), e->stream));
-  REC_CHK(hipMemsetAsync(t.claim, 0xFF, (size_t)t.num_bucket * 4, e->stream));
-  REC_CHK(hipMemsetAsync(t.dclaim, 0xFF, (size_t)t.num_bucket * 4, e->stream));
-  REC_CHK(hipMemsetAsync(e->dbitmap, 0, (size_t)e->dwords * 4, e->stream));
-  REC_CHK(hipMemsetAsync(e->dsummary, 0, (size_t)((e->dwords / kGroupWords + 31) / 32) * 4, e->stream));
+  StreamDrain drain{e->stream};
+  HIPCHK(hipMemsetAsync(t.occ, 0, (size_t)occ_words * 8, e->stream));
+  HIPCHK(hipMemsetAsync(t.active, 0xFF, nb * sizeof(VisItem), e->stream));
+  HIPCHK(hipMemsetAsync(t.claim, 0xFF, (size_t)t.num_bucket * 4, e->stream));
+  HIPCHK(hipMemsetAsync(t.dclaim, 0xFF, (size_t)t.num_bucket * 4, e->stream));
+  HIPCHK(hipMemsetAsync(e->dbitmap, 0, (size_t)e->dwords * 4, e->stream));
+  HIPCHK(hipMemsetAsync(e->dsummary, 0, (size_t)((e->dwords / kGroupWords + 31) / 32) * 4, e->stream));
   if (e->abitmap) {
-    REC_CHK(hipMemsetAsync(e->abitmap, 0, (size_t)e->awords_cap * 4, e->stream));
-    REC_CHK(hipMemsetAsync(e->asummary, 0, (size_t)e->asum_words * 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->abitmap, 0, (size_t)e->awords_cap * 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->asummary, 0, (size_t)e->asum_words * 4, e->stream));
   }
-  REC_CHK(hipMemsetAsync(e->cand_count, 0, 2 * kCandSegs * kCandCountStride * 4, e->stream));
-  for (int i = 0; i < 2; ++i) REC_CHK(hipMemsetAsync(e->upd_wg[i], 0, kUpdCounters * 4, e->stream));
-  REC_CHK(hipMemsetAsync(&e->ctl->fr[0], 0, 2 * sizeof(FrameCtl), e->stream));
+  HIPCHK(hipMemsetAsync(e->cand_count, 0, 2 * kCandSegs * kCandCountStride * 4, e->stream));
+  for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(e->upd_wg[i], 0, kUpdCounters * 4, e->stream));
+  HIPCHK(hipMemsetAsync(&e->ctl->fr[0], 0, 2 * sizeof(FrameCtl), e->stream));
   hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, unused, 1u, nb);
   hipLaunchKernelGGL(k_recover_scan, dim3((t.num_entry + 255) / 256), dim3(256), 0, e->stream, t, unused);
   if (!keep_heap) {
     uint32_t n_free = 0;
-    if (mask_positions(e, unused, nb, pos, tiles, d_total, &n_free) != RATSDF_OK) return fail(RATSDF_ERR_DEVICE);
+    STCHK(mask_positions(e, unused, nb, pos, tiles, d_total, &n_free));
     hipLaunchKernelGGL(k_recover_heap, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, unused, pos,
                        e->pool.heap, (int32_t)nb);
     const int32_t nf = (int32_t)n_free;
-    REC_CHK(hipMemcpyAsync(&e->ctl->num_free, &nf, 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(&e->ctl->num_free, &nf, 4, hipMemcpyHostToDevice, e->stream));
     // (the low-water mark only ever goes down: slots at or above it may have been in use; the rebuilt heap keeps the
     // never-used indices -- the lowest ones -- at its bottom, so the mark stays true.  A free count below it moves it.)
     int32_t low = 0;
-    REC_CHK(hipMemcpyAsync(&low, &e->ctl->free_low, 4, hipMemcpyDeviceToHost, e->stream));
-    REC_CHK(hipStreamSynchronize(e->stream));
-    if (nf < low) REC_CHK(hipMemcpyAsync(&e->ctl->free_low, &nf, 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(&low, &e->ctl->free_low, 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (nf < low) HIPCHK(hipMemcpyAsync(&e->ctl->free_low, &nf, 4, hipMemcpyHostToDevice, e->stream));
   }
   if (t.delta_on) {  // the delta log no longer describes what changed: the next export reports an overflow
     const uint32_t over = 0x80000000u;
-    REC_CHK(hipMemcpyAsync(t.del_count, &over, 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(t.del_count, &over, 4, hipMemcpyHostToDevice, e->stream));
   }
   const uint32_t zero = 0;
-  REC_CHK(hipMemcpyAsync(&e->ctl->error, &zero, 4, hipMemcpyHostToDevice, e->stream));
-  REC_CHK(hipGetLastError());
-  REC_CHK(hipStreamSynchronize(e->stream));
-#undef REC_CHK
+  HIPCHK(hipMemcpyAsync(&e->ctl->error, &zero, 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
   e->h_err[0] = e->h_err[1] = 0u;
   e->pending = false;
   e->cand_ready = false;
@@ -1818,24 +1843,18 @@ static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
 }
 
 int ratsdf_recover(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   return rebuild_derived(e, false);
 }
 
 int ratsdf_stream(ratsdf_engine* e, void** out) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, out);
   *out = (void*)e->stream;
   return RATSDF_OK;
 }
 
 int ratsdf_profile_enable(ratsdf_engine* e, int enable) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   KernelTimer& t = e->timer;
   const int st = t.drain(e->stream);
   t.on = enable != 0;
@@ -1846,9 +1865,7 @@ int ratsdf_profile_enable(ratsdf_engine* e, int enable) {
 }
 
 int ratsdf_profile_read_frames(ratsdf_engine* e, float* k_us, float* period_us, int capacity, int* n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !n || capacity < 0) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, n && capacity >= 0);
   KernelTimer& t = e->timer;
   const int st = t.read(e->stream, nullptr, nullptr);
   const int have = (int)t.k_us.size();
@@ -1863,223 +1880,31 @@ int ratsdf_profile_read_frames(ratsdf_engine* e, float* k_us, float* period_us, 
 }
 
 int ratsdf_profile_read(ratsdf_engine* e, double* ms, int64_t* launches) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   return e->timer.read(e->stream, ms, launches);
 }
 
 int ratsdf_num_active_blocks(ratsdf_engine* e, int32_t* out) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
+  ENTRY(e, out);
+  STCHK(e->settle());
   int32_t nf = 0;
-  { const int rs = e->read_small(&nf, &e->ctl->num_free, 4); if (rs != RATSDF_OK) return rs; }
+  STCHK(e->read_small(&nf, &e->ctl->num_free, 4));
   *out = e->tab.num_block - nf;
   return RATSDF_OK;
 }
 
 int ratsdf_last_frame_stats(ratsdf_engine* e, ratsdf_frame_stats* out) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  { const int rs = e->read_small(out, e->d_stats, sizeof(*out)); if (rs != RATSDF_OK) return rs; }
-  return RATSDF_OK;
-}
-
-// diagnostic: per-wave stamps of the LAST k_integrate launch (stamps build only)
-extern "C" int ratsdf_debug_wave_stamps(ratsdf_engine* e, int enable) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  // (one buffer per PROCESS, deliberately never freed and so without an owner: an engine's Ctl::debug_buf keeps
-  // pointing at it, and a static owner's destructor would call into a HIP runtime that is already shutting down)
-  static unsigned long long* buf = nullptr;
-  const size_t n = 16384 * 8;
-  if (enable > 0) {
-    if (!buf) HIPCHK(hipMalloc(&buf, n * 8));
-    HIPCHK(hipMemsetAsync(buf, 0, n * 8, e->stream));
-    HIPCHK(hipMemcpyAsync(&e->ctl->debug_buf, &buf, sizeof(buf), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return RATSDF_OK;
-  }
-  std::vector<unsigned long long> h(n);
-  HIPCHK(hipMemcpyAsync(h.data(), buf, n * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  // k_integrate keeps one half of the buffer per frame parity (the last two frames of a batch stay apart):
-  // enable = -1 / -2 reports the half of parity 0 / 1 alone
-  if (enable < 0) {
-    const size_t keep = (size_t)(-enable - 1);
-    for (size_t w = 0; w < 16384; ++w)
-      if ((w >> 13) != keep)
-        for (int k = 0; k < 8; ++k) h[w * 8 + k] = 0;
-  }
-  unsigned long long t0 = ~0ull, t1 = 0;
-  double ph[4] = {0, 0, 0, 0};
-  size_t cnt = 0;
-  std::vector<unsigned long long> starts, ends;
-  for (size_t w = 0; w < 16384; ++w) {
-    const unsigned long long* s = &h[w * 8];
-    if (!s[0] || !s[4] || !s[1]) continue;
-    t0 = s[5] < t0 ? s[5] : t0;
-    t1 = s[6] > t1 ? s[6] : t1;
-    ph[0] += (double)(s[1] - s[0]);
-    ph[1] += (double)(s[2] - s[1]);
-    ph[2] += (double)(s[3] - s[2]);
-    ph[3] += (double)(s[4] - s[3]);
-    starts.push_back(s[5]);
-    ends.push_back(s[6]);
-    ++cnt;
-  }
-  if (!cnt) { fprintf(stderr, "[wave stamps] none\n"); return RATSDF_OK; }
-  {  // phase profile of the slowest 5 % of the waves
-    std::vector<std::pair<unsigned long long, size_t>> dur;
-    for (size_t w = 0; w < 16384; ++w) {
-      const unsigned long long* s = &h[w * 8];
-      if (!s[0] || !s[4] || !s[1]) continue;
-      dur.emplace_back(s[4] - s[0], w);
-    }
-    std::sort(dur.begin(), dur.end());
-    const size_t lo = dur.size() * 95 / 100;
-    double q[4] = {0, 0, 0, 0};
-    for (size_t i = lo; i < dur.size(); ++i) {
-      const unsigned long long* s = &h[dur[i].second * 8];
-      q[0] += (double)(s[1] - s[0]); q[1] += (double)(s[2] - s[1]);
-      q[2] += (double)(s[3] - s[2]); q[3] += (double)(s[4] - s[3]);
-    }
-    const double m = (double)(dur.size() - lo);
-    fprintf(stderr, "[wave stamps] wave duration cycles: p50 %llu p95 %llu max %llu; slowest 5%% phases: %.0f | %.0f | %.0f | %.0f\n",
-            dur[dur.size() / 2].first, dur[lo].first, dur.back().first, q[0] / m, q[1] / m, q[2] / m, q[3] / m);
-  }
-  std::sort(starts.begin(), starts.end());
-  std::sort(ends.begin(), ends.end());
-  fprintf(stderr, "[wave stamps] %zu waves (first block of each); span first-start..last-end = %llu ticks of 10 ns\n", cnt, t1 - t0);
-  fprintf(stderr, "[wave stamps] mean cycles per phase: %.0f | %.0f | %.0f | %.0f  (k_integrate: issue+project | wait loads | math | store; k_front pixels with RATSDF_DEBUG=8: load+texel | ray math | wait lookups | evaluate)\n",
-          ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt);
-  fprintf(stderr, "[wave stamps] start spread: p50 %llu p99 %llu max %llu ; end: p1 %llu p50 %llu (relative to first start)\n",
-          starts[cnt / 2] - t0, starts[cnt * 99 / 100] - t0, starts[cnt - 1] - t0, ends[cnt / 100] - t0, ends[cnt / 2] - t0);
-  {  // the whole launch: when the serial role published, when the waves' LAST passes ended
-    unsigned long long st[6], last = 0;
-    std::vector<unsigned long long> done;
-    for (size_t w = 0; w < 16384; ++w)
-      if (h[w * 8 + 7]) done.push_back(h[w * 8 + 7]);
-    HIPCHK(hipMemcpyAsync(st, e->ctl->stamps, sizeof(st), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (!done.empty()) {
-      std::sort(done.begin(), done.end());
-      last = done.back();
-      for (int par = 0; par < 2; ++par)
-        if ((enable == 0 || par == -enable - 1) && st[par * 3 + 1] > t0 && st[par * 3 + 1] < last)
-          fprintf(stderr, "[wave stamps] serial role: started %lld, published at %lld; waves' last passes end: p50 %llu p99 %llu max %llu (10 ns ticks after the first update wave started)\n",
-                  (long long)(st[par * 3] - t0), (long long)(st[par * 3 + 1] - t0), done[done.size() / 2] - t0,
-                  done[done.size() * 99 / 100] - t0, last - t0);
-    }
-  }
-  return RATSDF_OK;
-}
-
-#ifdef RATSDF_STAMPS
-// diagnostic (stamps build only): the ablation / fault-injection switch of an engine after its creation (RATSDF_DEBUG
-// sets it at creation): tests/test_gpu_errors.py injects a fault, switches it off and recovers
-extern "C" int ratsdf_debug_set_switch(ratsdf_engine* e, int value) {
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
-  e->debug = value;
-  return RATSDF_OK;
-}
-#endif
-
-// diagnostic (stamps build only): the raw per-wave record buffer ratsdf_debug_wave_stamps(e, 1) attached (16 384 x 8
-// words), copied out and zeroed -- k_raycast's per-wave timeline (tools/raycast_probe.py)
-extern "C" int ratsdf_debug_wave_records(ratsdf_engine* e, unsigned long long* out, size_t words) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out || words > 16384 * 8) return RATSDF_ERR_BAD_ARGUMENT;
-  unsigned long long* buf = nullptr;
-  HIPCHK(hipMemcpyAsync(&buf, &e->ctl->debug_buf, sizeof(buf), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  if (!buf) return RATSDF_ERR_BAD_ARGUMENT;
-  HIPCHK(hipMemcpyAsync(out, buf, words * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RATSDF_OK;
-}
-
-// diagnostic (stamps build only): Ctl::dbg -- RATSDF_DEBUG=30 counts update waves that changed no voxel:
-// [0] such waves, [1] waves, [2] blocks without an update, [3] blocks; read and reset
-extern "C" int ratsdf_debug_counters(ratsdf_engine* e, unsigned long long* out8) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out8) return RATSDF_ERR_BAD_ARGUMENT;
-  HIPCHK(hipMemcpyAsync(out8, e->ctl->dbg, 8 * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemsetAsync(e->ctl->dbg, 0, 8 * 8, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RATSDF_OK;
-}
-
-// diagnostic: timeline of k_front's tail (stamps build only): sums over frames of wall-clock ticks (10 ns)
-// since the launch's first workgroup started
-extern "C" int ratsdf_debug_tail_stamps(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  unsigned long long t[16];
-  HIPCHK(hipMemcpyAsync(t, e->ctl->tstamps, sizeof(t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemsetAsync(e->ctl->tstamps, 0, sizeof(t), e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const double n = t[8] ? (double)t[8] : 1.0;
-  fprintf(stderr, "[tail stamps] %llu tail frames; us after the launch's first workgroup started: last directory workgroup "
-          "done %.2f | its stores drained %.2f | it knows it is last %.2f | tail: first round of loads in %.2f | claims + "
-          "winners listed %.2f | commits issued %.2f | end %.2f ; requests %.1f winners %.1f per frame\n",
-          t[8], t[1] / n / 100, t[2] / n / 100, t[3] / n / 100, t[4] / n / 100, t[5] / n / 100, t[6] / n / 100,
-          t[7] / n / 100, t[9] / n, t[10] / n);
-  if (t[15]) {
-    const double m = (double)t[15];
-    unsigned long long c[32];
-    HIPCHK(hipMemcpyAsync(c, e->ctl->stamps, sizeof(c), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const double k = c[17] ? (double)c[17] : 1.0;
-    fprintf(stderr, "[cand stamps] %llu candidate workgroups sampled (wave 0), shader cycles: inputs arrive %.0f | ray set-up %.0f | "
-            "sample loop %.0f (%.2f iterations) ; workgroup: set init + barrier %.0f | pixel work %.0f | barrier wait %.0f | "
-            "compaction + stores %.0f\n",
-            t[15], t[11] / m, t[12] / m, t[13] / m, t[14] / m, c[14] / k, c[15] / k, c[16] / k, c[18] / k);
-  }
-  return RATSDF_OK;
-}
-
-// diagnostic: prints the accumulated phase stamps of the single-workgroup kernels (stamps build only)
-extern "C" int ratsdf_debug_stamps(ratsdf_engine* e) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  unsigned long long t[32];
-  unsigned long long tot[5];
-  HIPCHK(hipMemcpyAsync(t, e->ctl->stamps, sizeof(t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(tot, e->ctl->totals, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const double n = tot[0] ? (double)tot[0] : 1.0;
-  fprintf(stderr, "[stamps] frames=%llu  serial role (shader cycles/frame): loads:%.0f claims+barrier:%.0f lists:%.0f ranks:%.0f tail:%.0f | deletes %.1f winners %.1f requests %.1f per frame\n",
-          tot[0], (double)(t[9] - t[8]) / n, (double)(t[10] - t[9]) / n, (double)(t[11] - t[10]) / n,
-          (double)(t[12] - t[11]) / n, (double)(t[13] - t[12]) / n, (double)t[16] / n, (double)t[17] / n,
-          (double)t[18] / n);
-  if (t[29])
-    fprintf(stderr, "[stamps] chained-bucket resolver, %llu passes (shader cycles/pass): order + duplicates %.0f | plans %.0f | replay %.0f | apply %.0f | per pass: requests %.1f distinct %.1f stale plans %.2f placed %.1f | step loop %.0f cycles for %.1f steps\n",
-            t[29], (double)(t[22] - t[20]) / t[29], (double)(t[23] - t[22]) / t[29], (double)(t[24] - t[23]) / t[29],
-            (double)(t[21] - t[24]) / t[29], (double)t[25] / t[29], (double)t[26] / t[29], (double)t[27] / t[29],
-            (double)t[28] / t[29], (double)(long long)t[30] / t[29], (double)t[31] / t[29]);
-  fprintf(stderr, "[stamps] ranks phase, first pass (cold code) %.0f cycles of the two\n", (double)t[19] / n);
-  {
-    const double m = t[17] ? (double)t[17] : 1.0;
-    fprintf(stderr, "[stamps] candidate pass, thread 0 of sampled workgroups (shader cycles): first barrier %.0f | pixel work %.0f | wait for the workgroup %.0f | compaction + stores %.0f\n",
-            (double)t[14] / m, (double)t[15] / m, (double)t[16] / m, (double)t[18] / m);
-  }
+  ENTRY(e, out);
+  STCHK(e->settle());
+  STCHK(e->read_small(out, e->d_stats, sizeof(*out)));
   return RATSDF_OK;
 }
 
 int ratsdf_totals(ratsdf_engine* e, int64_t* out5, int reset) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
+  ENTRY(e, true);
+  STCHK(e->settle());
   unsigned long long t[5] = {0, 0, 0, 0, 0};
-  { const int rs = e->read_small(t, e->ctl->totals, sizeof(t)); if (rs != RATSDF_OK) return rs; }
+  STCHK(e->read_small(t, e->ctl->totals, sizeof(t)));
   if (reset) HIPCHK(hipMemsetAsync(e->ctl->totals, 0, sizeof(t), e->stream));
   if (out5)
     for (int i = 0; i < 5; ++i) out5[i] = (int64_t)t[i];
@@ -2087,817 +1912,12 @@ int ratsdf_totals(ratsdf_engine* e, int64_t* out5, int reset) {
 }
 
 int ratsdf_pipeline_counters(ratsdf_engine* e, int64_t* out4, int reset) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
+  ENTRY(e, true);
   unsigned long long t[4] = {0, 0, 0, 0};
-  { const int rs = e->read_small(t, e->ctl->paths, sizeof(t)); if (rs != RATSDF_OK) return rs; }
+  STCHK(e->read_small(t, e->ctl->paths, sizeof(t)));
   if (reset) HIPCHK(hipMemsetAsync(e->ctl->paths, 0, sizeof(t), e->stream));
   if (out4)
     for (int i = 0; i < 4; ++i) out4[i] = (int64_t)t[i];
-  return RATSDF_OK;
-}
-
-// Device and page-locked staging buffers of the query-side downloads: kept between calls and only
-// ever grown (a hipMalloc / hipFree pair and a pageable D2H copy per Query cost more than the kernels).
-static int ensure_download_buffers(ratsdf_engine* e, size_t bytes) {
-  return e->grow_pair(e->dl_dev, e->dl_host, bytes, bytes + bytes / 4);
-}
-
-static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t* n) {
-  uint32_t cnt = 0;
-  { const int rs = e->read_small(&cnt, &e->ctl->n_sel, 4); if (rs != RATSDF_OK) return rs; }
-  const size_t rec = semantic ? sizeof(ratsdf_voxel_segm) : sizeof(ratsdf_voxel_tsdf);
-  const size_t total = (size_t)cnt * RATSDF_BLOCK_VOLUME;
-  void* host = malloc(total ? total * rec : 1);
-  if (!host) return RATSDF_ERR_DEVICE;
-  if (total) {
-    const int st = ensure_download_buffers(e, total * rec);
-    if (st != RATSDF_OK) {
-      free(host);
-      return st;
-    }
-    float* dev = e->dl_dev.as<float>();
-    const uint8_t* dl_host = e->dl_host.as<uint8_t>();
-    const unsigned grid = cnt < 4096u ? (cnt + 3) / 4 : 1024u;
-    if (semantic)
-      hipLaunchKernelGGL(k_download<true>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
-                         &e->ctl->n_sel, e->vs, dev);
-    else
-      hipLaunchKernelGGL(k_download<false>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
-                         &e->ctl->n_sel, e->vs, dev);
-    hipError_t err = hipMemcpyAsync(e->dl_host.as<void>(), dev, total * rec, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) {
-      free(host);
-      return RATSDF_ERR_DEVICE;
-    }
-    // the caller owns `host` (ratsdf_free_buffer).  A large result is copied out by the engine's helper threads side
-    // by side: the destination is fresh memory, and first-touch page faults (10 k of them for the 41 MB of a
-    // GatherValid on the bench map) are what the single-threaded copy spent most of its time on
-    const size_t bytes = total * rec;
-    HostCopyPool* cp = bytes >= ((size_t)4 << 20) ? e->host_copy_pool() : nullptr;
-    if (cp) {
-      HostCopyPool::Piece pieces[16];
-      int np = 0;
-      const size_t step = ((bytes + 15) / 16 + 4095) & ~(size_t)4095;
-      for (size_t o = 0; o < bytes; o += step)
-        pieces[np++] = HostCopyPool::Piece{(uint8_t*)host + o, dl_host + o, std::min(step, bytes - o)};
-      cp->copy(pieces, np);
-    } else {
-      memcpy(host, dl_host, bytes);
-    }
-  }
-  *out = host;
-  *n = total;
-  return RATSDF_OK;
-}
-
-static inline int16_t host_f2s(float f) {  // static_cast<short>, BoundingCube::Scale
-  if (f != f) return 0;
-  if (f >= 2147483648.f) return (int16_t)2147483647;
-  if (f <= -2147483648.f) return (int16_t)(-2147483647 - 1);
-  return (int16_t)(int)f;
-}
-
-int ratsdf_query(ratsdf_engine* e, const ratsdf_bounds* b, ratsdf_voxel_tsdf** out, size_t* n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !b || !out || !n) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  const float scale = (float)(1. / e->vs);  // volumn.Scale<short>(1. / voxel_size_), voxel_tsdf.cu:534
-  GridBounds gb{host_f2s(b->xmin * scale), host_f2s(b->xmax * scale), host_f2s(b->ymin * scale),
-                host_f2s(b->ymax * scale), host_f2s(b->zmin * scale), host_f2s(b->zmax * scale)};
-  int st = e->select(kSelBounds, gb, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  return download_selected(e, false, (void**)out, n);
-}
-
-int ratsdf_gather_valid(ratsdf_engine* e, ratsdf_voxel_tsdf** out, size_t* n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out || !n) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  int st = e->select(kSelValid, GridBounds{}, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  return download_selected(e, false, (void**)out, n);
-}
-
-int ratsdf_gather_valid_semantic(ratsdf_engine* e, ratsdf_voxel_segm** out, size_t* n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !out || !n) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  int st = e->select(kSelValid, GridBounds{}, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  return download_selected(e, true, (void**)out, n);
-}
-
-int ratsdf_download_all(ratsdf_engine* e, const char* path) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !path) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  ratsdf_voxel_segm* buf = nullptr;
-  size_t n = 0;
-  const int st = ratsdf_gather_valid_semantic(e, &buf, &n);
-  if (st != RATSDF_OK) return st;
-  FILE* f = fopen(path, "wb");
-  if (!f) {
-    free(buf);
-    return RATSDF_ERR_BAD_ARGUMENT;
-  }
-  fwrite(buf, sizeof(ratsdf_voxel_segm), n, f);
-  fclose(f);
-  free(buf);
-  return RATSDF_OK;
-}
-
-int ratsdf_free_buffer(void* p) {
-  free(p);
-  return RATSDF_OK;
-}
-
-// rows [row0, row1) of the height x width rendering into device buffers that hold those rows
-static int raycast_rows_device(ratsdf_engine* e, const ratsdf_intrinsics* K, int height, int width,
-                               const ratsdf_pose* T, float max_depth, int row0, int row1, void* d_rgba,
-                               void* d_normal) {
-  if (!e || !K || !T || height <= 0 || width <= 0 || !(max_depth > 0) || row0 < 0 || row1 > height || row0 > row1)
-    return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (row0 == row1) return RATSDF_OK;
-  FrameParams P = e->base_params();
-  P.T = Se3{Quat{T->qx, T->qy, T->qz, T->qw}, V3{T->tx, T->ty, T->tz}};
-  P.Ti = se3_inverse(P.T);                      // voxel_tsdf.cu:892 cam_T_world.Inverse()
-  P.K = Intr{K->fx, K->fy, K->cx, K->cy};
-  P.Ki = intr_inverse(P.K);
-  P.W = width;
-  P.H = height;
-  const float step_size = e->trunc / 2;         // voxel_tsdf.cu:892
-  const float ms = ceilf(max_depth / step_size);
-  const int max_step = ms >= 2147483648.f ? 2147483647 : (int)ms;  // voxel_tsdf.cu:298
-  // block-level occupancy of the map as it is now (kernels_raycast.h: empty space costs no directory probes)
-  STCHK(e->d_occ.grow((kOccWords + kCellWords) * 4));
-  uint32_t* const d_occ = e->d_occ.as<uint32_t>();
-  HIPCHK(hipMemsetAsync(d_occ, 0, (kOccWords + kCellWords) * 4, e->stream));
-  hipLaunchKernelGGL(k_occupancy_build, dim3(256), dim3(256), 0, e->stream, e->tab, (const Ctl*)e->ctl, d_occ);
-  hipLaunchKernelGGL(k_raycast, dim3((width + 15) / 16, (row1 - row0 + 15) / 16), dim3(256), 0, e->stream,
-                     e->tab, e->pool, P, step_size, max_step, (uint32_t*)d_rgba, (uint32_t*)d_normal, row0, row1,
-                     (const uint32_t*)d_occ, e->ctl);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-int ratsdf_raycast_device(ratsdf_engine* e, const ratsdf_intrinsics* K, int height, int width,
-                          const ratsdf_pose* T, float max_depth, void* d_rgba, void* d_normal) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  return raycast_rows_device(e, K, height, width, T, max_depth, 0, height, d_rgba, d_normal);
-}
-
-int ratsdf_raycast_rows(ratsdf_engine* e, const ratsdf_intrinsics* K, int height, int width,
-                        const ratsdf_pose* T, float max_depth, int row0, int row1, uint8_t* rgba, uint8_t* normal) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || height <= 0 || width <= 0 || row0 < 0 || row1 > height || row0 > row1) return RATSDF_ERR_BAD_ARGUMENT;
-  const size_t bytes = (size_t)(row1 - row0) * width * 4;
-  if (bytes == 0) return raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, nullptr, nullptr);
-  // The two images leave through buffers the engine keeps: device memory for the kernel's output and page-locked host
-  // memory for the copy out (until round 5: a hipMalloc / hipFree pair per call and two copies into the caller's
-  // pageable buffers through the runtime's staging path -- 0.84 ms per 640x480 rendering of which the kernel was half).
-  STCHK(e->grow_pair(e->d_render, e->h_render, bytes * 2, bytes * 2));
-  uint8_t* d = e->d_render.as<uint8_t>();
-  uint8_t* h = e->h_render.as<uint8_t>();
-  STCHK(raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, d, d + bytes));
-  HIPCHK(hipMemcpyAsync(h, d, bytes * 2, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));  // voxel_tsdf.cu:901
-  if (rgba) memcpy(rgba, h, bytes);
-  if (normal) memcpy(normal, h + bytes, bytes);
-  return RATSDF_OK;
-}
-
-int ratsdf_raycast(ratsdf_engine* e, const ratsdf_intrinsics* K, int height, int width,
-                   const ratsdf_pose* T, float max_depth, uint8_t* rgba, uint8_t* normal) {
-  return ratsdf_raycast_rows(e, K, height, width, T, max_depth, 0, height, rgba, normal);
-}
-
-// ---- point sampling (include/ratsdf_sample.h, kernels_sample.h) ---------------------------------
-constexpr size_t kSampleChunk = (size_t)1 << 21;  // points per staged pass of the host entry point (88 MiB of buffers)
-constexpr size_t kSampleRecord = 32, kSamplePoint = 12;
-
-// a sticky error some finished launch has already raised, without waiting for the stream (ratsdf_engine::sticky)
-static int sticky_raised(ratsdf_engine* e) {
-  return *(volatile uint32_t*)e->h_err != 0u ? e->sticky() : RATSDF_OK;
-}
-
-static int sample_launch(ratsdf_engine* e, const float* d_xyz, size_t n, void* d_out) {
-  hipLaunchKernelGGL(k_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->tab, e->pool, d_xyz,
-                     (int)n, e->vs, (uint4*)d_out);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-int ratsdf_sample_points_device(ratsdf_engine* e, const void* d_xyz, size_t n, void* d_out) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (n > 0 && (!d_xyz || !d_out)) || n > (size_t)INT32_MAX || ((uintptr_t)d_out & 15u) ||
-      ((uintptr_t)d_xyz & 3u))
-    return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  { const int st0 = sticky_raised(e); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return RATSDF_OK;
-  return sample_launch(e, (const float*)d_xyz, n, d_out);
-}
-
-int ratsdf_sample_points(ratsdf_engine* e, const float* xyz, size_t n, ratsdf_sample* out) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (n > 0 && (!xyz || !out)) || n > (size_t)INT32_MAX) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return e->sticky();
-  // points in and records out through buffers the engine keeps, grown on demand (as the ray cast's d_render /
-  // h_render); their capacity in points is what they hold
-  const size_t chunk = std::min(n, kSampleChunk);
-  const size_t per = kSampleRecord + kSamplePoint;
-  STCHK(e->grow_pair(e->d_sample, e->h_sample, chunk * per, chunk * per));
-  const size_t cap = e->d_sample.size() / per;
-  uint8_t* d_rec = e->d_sample.as<uint8_t>();
-  float* d_pts = (float*)(d_rec + cap * kSampleRecord);
-  uint8_t* h_rec = e->h_sample.as<uint8_t>();
-  float* h_pts = (float*)(h_rec + cap * kSampleRecord);
-  for (size_t o = 0; o < n; o += chunk) {
-    const size_t m = std::min(chunk, n - o);
-    memcpy(h_pts, xyz + 3 * o, m * kSamplePoint);
-    HIPCHK(hipMemcpyAsync(d_pts, h_pts, m * kSamplePoint, hipMemcpyHostToDevice, e->stream));
-    STCHK(sample_launch(e, d_pts, m, d_rec));
-    HIPCHK(hipMemcpyAsync(h_rec, d_rec, m * kSampleRecord, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    memcpy(out + o, h_rec, m * kSampleRecord);
-  }
-  return e->sticky();
-}
-
-// ---- Euclidean signed distance field over a box (include/ratsdf_esdf.h, kernels_esdf.h) ---------
-constexpr size_t kEsdfMaxVoxels = (size_t)1 << 27;
-constexpr size_t kEsdfHostChunk = (size_t)32 << 20;  // bytes of the host entry point's page-locked pass-through
-
-// the workspace of a box of n voxels: state (n B) | x pass (4n B; the host entry point's field after the z pass) |
-// y pass (8n B) | stack of the transform to O (8n B) | stack of the transform to box \ O (8n B)
-struct EsdfWork {
-  uint8_t* st;
-  uint32_t* gx;
-  uint2 *gy, *stk0, *stk1;
-};
-static size_t esdf_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-static size_t esdf_work_bytes(size_t n) { return esdf_round(n) + esdf_round(4 * n) + 3 * esdf_round(8 * n); }
-
-// argument checks of both entry points (RATSDF_ERR_BAD_ARGUMENT when false)
-static bool esdf_box(const int32_t* origin, const int32_t* dims, float occupied_below, uint32_t flags, EsdfBox* b,
-                     size_t* n) {
-  if (!origin || !dims || std::isnan(occupied_below) || (flags & ~RATSDF_ESDF_UNKNOWN_OCCUPIED)) return false;
-  size_t m = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > 1024 || origin[a] < -32768 || (int64_t)origin[a] + dims[a] - 1 > 32767) return false;
-    m *= (size_t)dims[a];
-  }
-  if (m > kEsdfMaxVoxels) return false;
-  b->ox = origin[0], b->oy = origin[1], b->oz = origin[2];
-  b->X = dims[0], b->Y = dims[1], b->Z = dims[2];
-  b->bx0 = origin[0] >> 3, b->by0 = origin[1] >> 3, b->bz0 = origin[2] >> 3;
-  b->nbx = ((origin[0] + dims[0] - 1) >> 3) - b->bx0 + 1;
-  b->nby = ((origin[1] + dims[1] - 1) >> 3) - b->by0 + 1;
-  *n = m;
-  return true;
-}
-
-// a workspace for n voxels (laid out for the number it was allocated for)
-static int esdf_workspace(ratsdf_engine* e, size_t n, EsdfWork* w) {
-  if (e->esdf_cap < n) {
-    HIPCHK(hipStreamSynchronize(e->stream));  // an earlier field may still be using the old one
-    e->esdf_cap = 0;
-    STCHK(e->d_esdf.alloc(esdf_work_bytes(n)));
-    e->esdf_cap = n;
-  }
-  const size_t cap = e->esdf_cap;
-  uint8_t* p = e->d_esdf.as<uint8_t>();
-  w->st = p;
-  w->gx = (uint32_t*)(p += esdf_round(cap));
-  w->gy = (uint2*)(p += esdf_round(4 * cap));
-  w->stk0 = (uint2*)(p += esdf_round(8 * cap));
-  w->stk1 = (uint2*)(p += esdf_round(8 * cap));
-  return RATSDF_OK;
-}
-
-static int esdf_launch(ratsdf_engine* e, const EsdfBox& b, size_t n, float occupied_below, uint32_t flags,
-                       const EsdfWork& w, float* d_out, uint8_t* d_state) {
-  uint8_t* st = d_state ? d_state : w.st;
-  const int nbz = ((b.oz + b.Z - 1) >> 3) - b.bz0 + 1;
-  hipLaunchKernelGGL(k_esdf_seed, dim3((unsigned)(b.nbx * b.nby * nbz)), dim3(256), 0, e->stream, e->tab, e->pool, b,
-                     occupied_below, st);
-  HIPCHK(hipGetLastError());
-  const uint32_t omask = (1u << kEsdfOccupied) | ((flags & RATSDF_ESDF_UNKNOWN_OCCUPIED) ? 1u << kEsdfUnknown : 0u);
-  const uint32_t rows = (uint32_t)(n / (size_t)b.X);
-  hipLaunchKernelGGL(k_esdf_x, dim3((rows + 3) / 4), dim3(256), 0, e->stream, st, omask, b.X, rows, w.gx);
-  HIPCHK(hipGetLastError());
-  const uint32_t cy = (uint32_t)b.X * (uint32_t)b.Z, cz = (uint32_t)b.X * (uint32_t)b.Y;
-  hipLaunchKernelGGL(k_esdf_col<1>, dim3((cy + kEsdfColWG - 1) / kEsdfColWG), dim3(kEsdfColWG), 0, e->stream,
-                     (const void*)w.gx, b.Y, b.X, (uint32_t)b.X * (uint32_t)b.Y, (uint32_t)b.X, cy, w.stk0, w.stk1,
-                     (void*)w.gy, e->vs);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_esdf_col<2>, dim3((cz + kEsdfColWG - 1) / kEsdfColWG), dim3(kEsdfColWG), 0, e->stream,
-                     (const void*)w.gy, b.Z, b.X, (uint32_t)b.X, (uint32_t)b.X * (uint32_t)b.Y, cz, w.stk0, w.stk1,
-                     (void*)d_out, e->vs);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-int ratsdf_esdf_device(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3], float occupied_below,
-                       uint32_t flags, void* d_out, void* d_state) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  EsdfBox b;
-  size_t n = 0;
-  if (!e || !d_out || ((uintptr_t)d_out & 15u) || !esdf_box(origin, dims, occupied_below, flags, &b, &n))
-    return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  { const int st0 = sticky_raised(e); if (st0 != RATSDF_OK) return st0; }
-  EsdfWork w;
-  { const int st0 = esdf_workspace(e, n, &w); if (st0 != RATSDF_OK) return st0; }
-  return esdf_launch(e, b, n, occupied_below, flags, w, (float*)d_out, (uint8_t*)d_state);
-}
-
-int ratsdf_esdf(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3], float occupied_below,
-                uint32_t flags, float* out, uint8_t* state) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  EsdfBox b;
-  size_t n = 0;
-  if (!e || !out || !esdf_box(origin, dims, occupied_below, flags, &b, &n)) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  { const int st0 = sticky_raised(e); if (st0 != RATSDF_OK) return st0; }
-  EsdfWork w;
-  { const int st0 = esdf_workspace(e, n, &w); if (st0 != RATSDF_OK) return st0; }
-  STCHK(e->h_esdf.grow(kEsdfHostChunk));
-  uint8_t* const h = e->h_esdf.as<uint8_t>();
-  // the field lands in the x pass's buffer, dead once the y pass has run
-  { const int st0 = esdf_launch(e, b, n, occupied_below, flags, w, (float*)w.gx, nullptr); if (st0 != RATSDF_OK) return st0; }
-  const struct { const uint8_t* src; uint8_t* dst; size_t bytes; } parts[2] = {
-      {(const uint8_t*)w.gx, (uint8_t*)out, n * sizeof(float)}, {w.st, state, state ? n : 0}};
-  for (const auto& p : parts)
-    for (size_t o = 0; o < p.bytes; o += kEsdfHostChunk) {
-      const size_t m = std::min(kEsdfHostChunk, p.bytes - o);
-      HIPCHK(hipMemcpyAsync(h, p.src + o, m, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      memcpy(p.dst + o, h, m);
-    }
-  return e->sticky();
-}
-
-// exclusive positions of the set items of a 0/1 mask; returns the number of set items
-static int mask_positions(ratsdf_engine* e, const uint32_t* mask, size_t n, uint32_t* pos,
-                          uint32_t* scratch_tiles, uint32_t* d_total, uint32_t* h_total) {
-  const uint32_t ntiles = (uint32_t)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(k_mask_tile_sums, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, scratch_tiles, ntiles,
-                     d_total);
-  hipLaunchKernelGGL(k_mask_positions, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles,
-                     pos);
-  HIPCHK(hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RATSDF_OK;
-}
-
-int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_vertices,
-                             int32_t** indices, size_t* n_triangles, float** vertex_prob) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !vertices || !n_vertices || !indices || !n_triangles || !vertex_prob)
-    return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  // check_valid_kernel + GatherBlock; a sharded map meshes the blocks it owns (imported neighbours are read only)
-  int st = e->select(e->shard_count > 1 ? kSelOwned : kSelValid, GridBounds{}, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  uint32_t nb = 0;
-  HIPCHK(hipMemcpyAsync(&nb, &e->ctl->n_sel, 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  *vertices = (float*)malloc(4);
-  *vertex_prob = (float*)malloc(4);
-  *indices = (int32_t*)malloc(4);
-  *n_vertices = 0;
-  *n_triangles = 0;
-  if (nb == 0) return RATSDF_OK;
-  const size_t nvs = (size_t)nb * kVertVolume * 3;  // candidate vertices
-  const size_t nts = (size_t)nb * 512 * 5;          // candidate triangles
-  if (!e->d_mc) {
-    const McTables h = make_mc_tables();
-    DevMem mc;  // (the engine keeps tables that have arrived, nothing else)
-    STCHK(mc.alloc(sizeof(McTables)));
-    HIPCHK(hipMemcpy(mc.as<void>(), &h, sizeof(McTables), hipMemcpyHostToDevice));
-    e->d_mc = std::move(mc);
-  }
-  // one scratch allocation: verts | vprob | vmask | vpos | tids | tmask | tpos | tile sums | total
-  const size_t ntile_max = (nts > nvs ? nts : nvs) / kScanTile + 2;
-  const size_t bytes = nvs * 12 + nvs * 4 * 3 + nts * 12 + nts * 4 * 2 + ntile_max * 4 + 64;
-  DevMem d;
-  STCHK(d.alloc(bytes));
-  float* verts = d.as<float>();
-  float* vprob = verts + nvs * 3;
-  uint32_t* vmask = (uint32_t*)(vprob + nvs);
-  uint32_t* vpos = vmask + nvs;
-  int32_t* tids = (int32_t*)(vpos + nvs);
-  uint32_t* tmask = (uint32_t*)(tids + nts * 3);
-  uint32_t* tpos = tmask + nts;
-  uint32_t* tiles = tpos + nts;
-  uint32_t* d_total = tiles + ntile_max;
-  hipLaunchKernelGGL(k_marching_cubes, dim3(nb), dim3(512), 0, e->stream, e->tab, e->pool, e->vis,
-                     e->d_mc.as<const McTables>(), e->vs, verts, vprob, vmask, tids, tmask);
-  uint32_t nv = 0, nt = 0;
-  st = mask_positions(e, vmask, nvs, vpos, tiles, d_total, &nv);
-  if (st == RATSDF_OK) st = mask_positions(e, tmask, nts, tpos, tiles, d_total, &nt);
-  if (st != RATSDF_OK) return st;
-  free(*vertices);
-  free(*vertex_prob);
-  free(*indices);
-  *vertices = (float*)malloc((size_t)nv * 12 + 4);
-  *vertex_prob = (float*)malloc((size_t)nv * 4 + 4);
-  *indices = (int32_t*)malloc((size_t)nt * 12 + 4);
-  DevMem o;
-  STCHK(o.alloc((size_t)nv * 16 + (size_t)nt * 12 + 64));
-  float* ov = o.as<float>();
-  float* op = ov + (size_t)nv * 3;
-  int32_t* oi = (int32_t*)(op + nv);
-  hipLaunchKernelGGL(k_compact_vertices, dim3(2048), dim3(256), 0, e->stream, verts, vprob, vmask,
-                     vpos, nvs, ov, op);
-  hipLaunchKernelGGL(k_compact_triangles, dim3(2048), dim3(256), 0, e->stream, tids, tmask, tpos,
-                     vpos, nts, oi);
-  hipError_t err = hipSuccess;
-  if (nv) err = hipMemcpyAsync(*vertices, ov, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess && nv)
-    err = hipMemcpyAsync(*vertex_prob, op, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess && nt)
-    err = hipMemcpyAsync(*indices, oi, (size_t)nt * 12, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  if (err != hipSuccess) return RATSDF_ERR_DEVICE;
-  *n_vertices = nv;
-  *n_triangles = nt;
-  return RATSDF_OK;
-}
-
-int ratsdf_download_all_mesh(ratsdf_engine* e, const char* vp, const char* ip, const char* pp) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !vp || !ip || !pp) return RATSDF_ERR_BAD_ARGUMENT;
-  float *v = nullptr, *pr = nullptr;
-  int32_t* idx = nullptr;
-  size_t nv = 0, nt = 0;
-  int st = ratsdf_gather_valid_mesh(e, &v, &nv, &idx, &nt, &pr);
-  if (st == RATSDF_OK) {  // modules/tsdf_module.cc:66-86
-    FILE* fv = fopen(vp, "wb");
-    FILE* fp = fopen(pp, "wb");
-    FILE* fi = fopen(ip, "wb");
-    if (fv && fp && fi) {
-      fwrite(v, 12, nv, fv);
-      fwrite(pr, 4, nv, fp);
-      fwrite(idx, 12, nt, fi);
-    } else {
-      st = RATSDF_ERR_BAD_ARGUMENT;
-    }
-    if (fv) fclose(fv);
-    if (fp) fclose(fp);
-    if (fi) fclose(fi);
-  }
-  free(v);
-  free(pr);
-  free(idx);
-  return st;
-}
-
-int ratsdf_export_directory_device(ratsdf_engine* e, void* d_blocks, int32_t capacity,
-                                   void* d_count) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !d_blocks || capacity < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  int st = e->select(kSelValid, GridBounds{}, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  hipLaunchKernelGGL(k_export_entries, dim3(256), dim3(256), 0, e->stream, e->vis, &e->ctl->n_sel,
-                     (Entry*)d_blocks, (int32_t*)nullptr, (uint32_t)capacity, (int32_t*)d_count, e->ctl);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-// What the directory gained, changed and lost since the previous call (or since creation): the engine keeps a
-// dirty bit per entry and a log of deleted positions (device_types.h: Table::dirty / del_log), so the delta costs
-// two small kernels instead of a sort of the whole directory on the caller's side.  d_payload receives the
-// added / changed entries first, then one entry {position, offset 0, idx -1} per deleted position; d_counts
-// (int32[2]) the TRUE numbers of both -- more than `capacity` together means the payload was too small, and
-// 0x7FFFFFFF deleted positions that the log overflowed: either way the caller takes a whole directory
-// (ratsdf_export_directory_device) next.  A position deleted and inserted again is in both lists: drop, then add.
-// d_payload == NULL: forget the changes so far (after a whole-directory export).  Asynchronous on the engine's stream.
-int ratsdf_export_directory_delta_device(ratsdf_engine* e, void* d_payload, int32_t capacity, void* d_counts) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || capacity < 0 || (d_payload && !d_counts)) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  const uint32_t occ_words = (e->tab.num_entry + 63) / 64;
-  if (!e->tab.delta_on) {
-    // The first call starts the bookkeeping (an engine nobody asks for deltas keeps none: a dirty-bit atomic per
-    // commit and the delete log cost the frame 0.9 us).  Nothing has been recorded so far, so this call cannot
-    // deliver a delta: a payload call reports the overflow value and the caller takes a whole directory.
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->tab.delta_on = 1;
-    const int st1 = e->upload_record();
-    if (st1 != RATSDF_OK) return st1;
-    HIPCHK(hipMemsetAsync(e->tab.occ + occ_words, 0, (size_t)occ_words * 8, e->stream));
-    HIPCHK(hipMemsetAsync(e->tab.del_count, 0, 4, e->stream));
-    if (d_payload) {
-      const int32_t unusable[2] = {0, 0x7FFFFFFF};
-      HIPCHK(hipMemcpyAsync(d_counts, unusable, 8, hipMemcpyHostToDevice, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    return RATSDF_OK;
-  }
-  if (!d_payload) {
-    HIPCHK(hipMemsetAsync(e->tab.occ + occ_words, 0, (size_t)occ_words * 8, e->stream));
-    HIPCHK(hipMemsetAsync(e->tab.del_count, 0, 4, e->stream));
-    return RATSDF_OK;
-  }
-  HIPCHK(hipMemsetAsync(d_counts, 0, 8, e->stream));
-  hipLaunchKernelGGL(k_delta_added, dim3(e->nwg), dim3(kVisWG), 0, e->stream, e->tab, (Entry*)d_payload,
-                     (uint32_t)capacity, (uint32_t*)d_counts);
-  hipLaunchKernelGGL(k_delta_deleted, dim3(64), dim3(256), 0, e->stream, e->tab, (Entry*)d_payload,
-                     (uint32_t)capacity, (uint32_t*)d_counts);
-  hipLaunchKernelGGL(k_delta_reset, dim3(1), dim3(1), 0, e->stream, e->tab);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-// ---- test hooks ------------------------------------------------------------------------------
-static int upload_s3(ratsdf_engine* e, const int16_t* src, int32_t n, DevMem* dev) {
-  if (n == 0) return RATSDF_OK;
-  STCHK(dev->alloc((size_t)n * 6));
-  HIPCHK(hipMemcpyAsync(dev->as<void>(), src, (size_t)n * 6, hipMemcpyHostToDevice, e->stream));
-  return RATSDF_OK;
-}
-
-int ratsdf_test_allocate(ratsdf_engine* e, const int16_t* bp, int32_t n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (!bp && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return e->sticky();
-  STCHK(e->ensure_image(0, (size_t)n));
-  DevMem d_bp;
-  STCHK(upload_s3(e, bp, n, &d_bp));
-  const int16_t* d = d_bp.as<int16_t>();
-  FrameParams P = e->base_params();
-  const uint32_t par = e->parity;  // an allocation pass of its own in the next frame's counters
-  hipLaunchKernelGGL(k_alloc_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, P, d, n,
-                     e->req, e->req_cap, e->slow, kSlowCap, e->ctl, par);
-  const int st = e->alloc_rank((uint32_t)n, par);
-  hipLaunchKernelGGL(k_commit_only, dim3(256), dim3(256), 0, e->stream, e->tab, e->pool, e->req,
-                     e->req_cap, e->req_k, e->win_ranks, e->ctl, par);
-  // no deletes in this pass; k_settle just zeroes the counters again
-  hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par),
-                     e->ctl, par, (ratsdf_frame_stats*)nullptr);
-  const int st2 = e->sticky();  // (synchronises: nothing queued outlives the uploaded list)
-  return st != RATSDF_OK ? st : st2;
-}
-
-// The blocks at d_pos (device, n x 3 int16) into the directory -- whatever the engine's shard filter says -- and
-// their voxels from device arrays laid out as k_import_voxels describes.  Synchronises the engine's stream (the number
-// of blocks the directory still lacks after a pass is read back: control data, 4 bytes per pass).
-static int import_from_device(ratsdf_engine* e, int32_t n, const int16_t* d_pos, const float* d_tsdf,
-                              const uint32_t* d_rgbw, const float* d_prob, uint32_t stride) {
-  e->ever_sem = true;  // (the blocks come with their probabilities: FrameParams::segm_live)
-  int st = e->ensure_image(0, (size_t)n);
-  if (st != RATSDF_OK) return st;
-  DevMem missing_mem;
-  STCHK(missing_mem.alloc(4));
-  uint32_t* const d_missing = missing_mem.as<uint32_t>();
-  auto cleanup = [&](int status) {  // (nothing queued may outlive d_missing)
-    (void)hipStreamSynchronize(e->stream);
-    return status;
-  };
-  FrameParams P = e->base_params();
-  P.shard_count = 1;  // whatever the engine's shard filter says
-  uint32_t missing = (uint32_t)n;
-  // an insertion can lose its bucket to another one of the same pass (one per bucket and pass,
-  // voxel_hash.cu:67-78): allocate, copy, and go again for whatever the directory still lacks
-  for (int pass = 0; pass < 8 && missing != 0; ++pass) {
-    const uint32_t par = e->parity;
-    hipLaunchKernelGGL(k_alloc_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, P, d_pos, n, e->req,
-                       e->req_cap, e->slow, kSlowCap, e->ctl, par);
-    st = e->alloc_rank((uint32_t)n, par);
-    if (st != RATSDF_OK) return cleanup(st);
-    hipLaunchKernelGGL(k_commit_only, dim3(256), dim3(256), 0, e->stream, e->tab, e->pool, e->req, e->req_cap,
-                       e->req_k, e->win_ranks, e->ctl, par);
-    hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par), e->ctl, par,
-                       (ratsdf_frame_stats*)nullptr);
-    if (hipMemsetAsync(d_missing, 0, 4, e->stream) != hipSuccess) return cleanup(RATSDF_ERR_DEVICE);
-    hipLaunchKernelGGL(k_import_voxels, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->tab, e->pool, d_pos, n, d_tsdf,
-                       d_rgbw, d_prob, stride, d_missing);
-    if (hipMemcpyAsync(&missing, d_missing, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-      return cleanup(RATSDF_ERR_DEVICE);
-  }
-  st = e->sticky();
-  if (st == RATSDF_OK && missing != 0) st = RATSDF_ERR_CAPACITY;
-  return cleanup(st);
-}
-
-int ratsdf_import_blocks(ratsdf_engine* e, int32_t n, const int16_t* bp, const float* tsdf, const ratsdf_rgbw* rgbw,
-                         const float* prob) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || (n > 0 && (!bp || !tsdf || !rgbw || !prob))) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return e->sticky();
-  DevMem pos_mem, vox_mem;
-  const size_t per = (size_t)n * 512 * 4;
-  STCHK(upload_s3(e, bp, n, &pos_mem));
-  auto cleanup = [&](int status) {  // (nothing queued may outlive the two uploads)
-    (void)hipStreamSynchronize(e->stream);
-    return status;
-  };
-  if (vox_mem.alloc(per * 3) != RATSDF_OK) return cleanup(RATSDF_ERR_DEVICE);
-  const int16_t* d_pos = pos_mem.as<int16_t>();
-  uint8_t* d_vox = vox_mem.as<uint8_t>();
-  if (hipMemcpyAsync(d_vox, tsdf, per, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-      hipMemcpyAsync(d_vox + per, rgbw, per, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-      hipMemcpyAsync(d_vox + 2 * per, prob, per, hipMemcpyHostToDevice, e->stream) != hipSuccess)
-    return cleanup(RATSDF_ERR_DEVICE);
-  return cleanup(import_from_device(e, n, d_pos, (const float*)d_vox, (const uint32_t*)(d_vox + per),
-                                    (const float*)(d_vox + 2 * per), 512u));
-}
-
-int ratsdf_import_blocks_device(ratsdf_engine* e, int32_t n, const void* d_block_pos, const void* d_voxels) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || (n > 0 && (!d_block_pos || !d_voxels))) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return e->sticky();
-  const uint32_t* rec = (const uint32_t*)d_voxels;
-  return import_from_device(e, n, (const int16_t*)d_block_pos, (const float*)rec, rec + 512, (const float*)(rec + 1024),
-                            1536u);
-}
-
-int ratsdf_export_blocks_device(ratsdf_engine* e, int32_t n, const void* d_block_pos, void* d_voxels,
-                                void* d_missing) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || n < 0 || !d_missing || (n > 0 && (!d_block_pos || !d_voxels))) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  HIPCHK(hipMemsetAsync(d_missing, 0, 4, e->stream));
-  if (n == 0) return RATSDF_OK;
-  hipLaunchKernelGGL(k_export_blocks, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->tab, e->pool,
-                     (const int16_t*)d_block_pos, n, (uint32_t*)d_voxels, (uint32_t*)d_missing);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
-}
-
-int ratsdf_test_delete(ratsdf_engine* e, const int16_t* bp, int32_t n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (!bp && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  // keep the first occurrence of every position (a repeated Delete is a no-op in list order)
-  std::vector<int16_t> uniq;
-  uniq.reserve((size_t)n * 3);
-  for (int i = 0; i < n; ++i) {
-    bool dup = false;
-    for (size_t j = 0; j + 2 < uniq.size() && !dup; j += 3)
-      dup = uniq[j] == bp[3 * i] && uniq[j + 1] == bp[3 * i + 1] && uniq[j + 2] == bp[3 * i + 2];
-    if (!dup) uniq.insert(uniq.end(), bp + 3 * i, bp + 3 * i + 3);
-  }
-  const int32_t m = (int32_t)(uniq.size() / 3);
-  if (m == 0) return e->sticky();
-  if (m > e->tab.num_block) return RATSDF_ERR_BAD_ARGUMENT;
-  DevMem d_bp;
-  STCHK(upload_s3(e, uniq.data(), m, &d_bp));
-  const int16_t* d = d_bp.as<int16_t>();
-  const uint32_t par = e->parity;
-  hipLaunchKernelGGL(k_delete_list, dim3((m + 255) / 256), dim3(256), 0, e->stream, e->tab, d, m,
-                     e->carve_bufs(par), e->ctl, par);
-  hipLaunchKernelGGL(k_settle, dim3(1), dim3(1024), 0, e->stream, e->tab, e->pool, e->carve_bufs(par),
-                     e->ctl, par, (ratsdf_frame_stats*)nullptr);
-  return e->sticky();  // (synchronises: nothing queued outlives the uploaded list)
-}
-
-int ratsdf_test_retrieve(ratsdf_engine* e, const int16_t* pts, int32_t n, ratsdf_rgbw* rgbw,
-                         float* tsdf, float* prob, ratsdf_block* blocks) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (!pts && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return RATSDF_OK;
-  DevMem d_pts, d_res;
-  STCHK(upload_s3(e, pts, n, &d_pts));
-  STCHK(d_res.alloc((size_t)n * 24));
-  const int16_t* d = d_pts.as<int16_t>();
-  uint8_t* o = d_res.as<uint8_t>();
-  uint32_t* o_rgbw = (uint32_t*)o;
-  float* o_tsdf = (float*)(o + (size_t)n * 4);
-  float* o_prob = (float*)(o + (size_t)n * 8);
-  Entry* o_blk = (Entry*)(o + (size_t)n * 12);
-  hipLaunchKernelGGL(k_retrieve, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, e->pool, d,
-                     n, o_rgbw, o_tsdf, o_prob, o_blk);
-  std::vector<uint8_t> h((size_t)n * 24);
-  HIPCHK(hipMemcpyAsync(h.data(), o, h.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  if (rgbw) memcpy(rgbw, h.data(), (size_t)n * 4);
-  if (tsdf) memcpy(tsdf, h.data() + (size_t)n * 4, (size_t)n * 4);
-  if (prob) memcpy(prob, h.data() + (size_t)n * 8, (size_t)n * 4);
-  if (blocks) memcpy(blocks, h.data() + (size_t)n * 12, (size_t)n * 12);
-  return RATSDF_OK;
-}
-
-int ratsdf_test_assign_rgbw(ratsdf_engine* e, const int16_t* pts, const ratsdf_rgbw* vals,
-                            int32_t n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || ((!pts || !vals) && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return RATSDF_OK;
-  DevMem d_pts, d_vals;
-  STCHK(upload_s3(e, pts, n, &d_pts));
-  STCHK(d_vals.alloc((size_t)n * 4));
-  const int16_t* d = d_pts.as<int16_t>();
-  uint32_t* v = d_vals.as<uint32_t>();
-  HIPCHK(hipMemcpyAsync(v, vals, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_assign_rgbw, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->tab, e->pool,
-                     d, v, n);
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RATSDF_OK;
-}
-
-int ratsdf_dump_directory(ratsdf_engine* e, int32_t** entry_index, ratsdf_block** blocks,
-                          size_t* n) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || !entry_index || !blocks || !n) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  int st = e->select(kSelValid, GridBounds{}, &e->ctl->n_sel);
-  if (st != RATSDF_OK) return st;
-  uint32_t cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, &e->ctl->n_sel, 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  int32_t* ei = (int32_t*)malloc(cnt ? (size_t)cnt * 4 : 1);
-  ratsdf_block* bl = (ratsdf_block*)malloc(cnt ? (size_t)cnt * 12 : 1);
-  if (cnt) {
-    DevMem b_mem, e_mem;
-    STCHK(b_mem.alloc((size_t)cnt * 12));
-    STCHK(e_mem.alloc((size_t)cnt * 4));
-    Entry* d_b = b_mem.as<Entry>();
-    int32_t* d_e = e_mem.as<int32_t>();
-    hipLaunchKernelGGL(k_export_entries, dim3(256), dim3(256), 0, e->stream, e->vis, &e->ctl->n_sel,
-                       d_b, d_e, cnt, (int32_t*)nullptr, (Ctl*)nullptr);
-    HIPCHK(hipMemcpyAsync(bl, d_b, (size_t)cnt * 12, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(ei, d_e, (size_t)cnt * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-  }
-  *entry_index = ei;
-  *blocks = bl;
-  *n = cnt;
-  return RATSDF_OK;
-}
-
-int ratsdf_dump_voxels(ratsdf_engine* e, const int32_t* pool_idx, int32_t n, float* tsdf,
-                       ratsdf_rgbw* rgbw, float* prob) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e || (!pool_idx && n > 0) || n < 0) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (n == 0) return RATSDF_OK;
-  for (int i = 0; i < n; ++i)
-    if (pool_idx[i] < 0 || pool_idx[i] >= e->tab.num_block) return RATSDF_ERR_BAD_ARGUMENT;
-  DevMem idx_mem, out_mem;
-  const size_t per = (size_t)n * 512 * 4;
-  STCHK(idx_mem.alloc((size_t)n * 4));
-  STCHK(out_mem.alloc(per * 3));
-  int32_t* d_idx = idx_mem.as<int32_t>();
-  uint8_t* d_out = out_mem.as<uint8_t>();
-  HIPCHK(hipMemcpyAsync(d_idx, pool_idx, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_gather_voxels, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->pool, d_idx, n,
-                     (float*)d_out, (uint32_t*)(d_out + per), (float*)(d_out + 2 * per));
-  if (tsdf) HIPCHK(hipMemcpyAsync(tsdf, d_out, per, hipMemcpyDeviceToHost, e->stream));
-  if (rgbw) HIPCHK(hipMemcpyAsync(rgbw, d_out + per, per, hipMemcpyDeviceToHost, e->stream));
-  if (prob) HIPCHK(hipMemcpyAsync(prob, d_out + 2 * per, per, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RATSDF_OK;
-}
-
-int ratsdf_dump_heap(ratsdf_engine* e, int32_t* num_free, int32_t* heap) {
-  DeviceGuard guard(e ? e->device : -1);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  if (!e) return RATSDF_ERR_BAD_ARGUMENT;
-  { const int st0 = e->settle(); if (st0 != RATSDF_OK) return st0; }
-  if (num_free)
-    HIPCHK(hipMemcpyAsync(num_free, &e->ctl->num_free, 4, hipMemcpyDeviceToHost, e->stream));
-  if (heap)
-    HIPCHK(hipMemcpyAsync(heap, e->pool.heap, (size_t)e->tab.num_block * 4, hipMemcpyDeviceToHost,
-                          e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
   return RATSDF_OK;
 }
 
@@ -2918,241 +1938,14 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 
 }  // extern "C"
 
-// ================================== groups =====================================================
-// Several engines (maps) of one device stepped together: frame i of every member stream goes through
-// ONE k_front / k_alloc_rank / k_integrate triple whose grids have one slice per engine (blockIdx.y).
-// A single 640x480 frame leaves most of the chip waiting on memory round trips and launch ramps; S
-// frames per launch fill it.  Operands come from device tables: the engine records (device_types.h:
-// EngineDev) and a per-batch table of FrameJob {parameters, image pointers, parity} per frame and slot.
-struct ratsdf_group {
-  int device = 0;
-  int S = 0;
-  std::vector<ratsdf_engine*> eng;
-  hipStream_t stream = nullptr;
-  std::vector<hipEvent_t> ev_member;  // member stream -> group stream
-  hipEvent_t ev_done = nullptr;       // group stream -> member streams
-  DevMem d_engs, d_jobs;  // EngineDev[S]; FrameJob[frames of a batch x S], grown on demand
-  // page-locked staging of the tables, two of each, used alternately (a copy may still be pending
-  // when the next batch is being prepared)
-  HostMem h_engs[2], h_jobs[2];
-  hipEvent_t ev_stage[2] = {nullptr, nullptr};
-  unsigned batch_no = 0;
-  int split_a = 100, split_b = 0;  // look-ahead share of k_front / k_alloc_rank (rest: k_integrate)
-  KernelTimer timer;  // (mode 1: every fourth frame)
-
-  void free_all() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (DevMem* m : {&d_engs, &d_jobs}) m->reset();
-    for (int i = 0; i < 2; ++i) {
-      h_engs[i].reset();
-      h_jobs[i].reset();
-      if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
-    }
-    for (auto& ev : ev_member)
-      if (ev) (void)hipEventDestroy(ev);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    timer.destroy();
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-extern "C" {
-
-int ratsdf_group_create(ratsdf_engine* const* engines, int n, ratsdf_group** out) {
-  if (!engines || !out || n < 1 || n > 64) return RATSDF_ERR_BAD_ARGUMENT;
-  for (int i = 0; i < n; ++i) {
-    const ratsdf_engine* a = engines[i];
-    if (!a) return RATSDF_ERR_BAD_ARGUMENT;
-    const ratsdf_engine* b = engines[0];
-    // one launch geometry for all members
-    if (a->device != b->device || a->vs != b->vs || a->trunc != b->trunc ||
-        a->block_bits != b->block_bits || a->bucket_bits != b->bucket_bits || a->vpl != b->vpl)
-      return RATSDF_ERR_BAD_ARGUMENT;
-    for (int j = 0; j < i; ++j)
-      if (engines[j] == a) return RATSDF_ERR_BAD_ARGUMENT;
-  }
-  DeviceGuard guard(engines[0]->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  ratsdf_group* g = new (std::nothrow) ratsdf_group();
-  if (!g) return RATSDF_ERR_DEVICE;
-  g->device = engines[0]->device;
-  g->S = n;
-  g->eng.assign(engines, engines + n);
-  g->ev_member.assign((size_t)n, nullptr);
-#ifdef RATSDF_STAMPS
-  if (const char* v = getenv("RATSDF_GROUP_SPLIT")) {  // "a[,b]" like RATSDF_CAND_SPLIT
-    const int x = atoi(v);
-    if (x >= 0 && x <= 100) {
-      g->split_a = x;
-      g->split_b = 0;
-      if (const char* c = strchr(v, ',')) {
-        const int y = atoi(c + 1);
-        if (y >= 0 && x + y <= 100) g->split_b = y;
-      }
-    }
-  }
-#endif
-#define GROUP_CHK(expr)                                                  \
-  do {                                                                   \
-    if ((expr) != hipSuccess) {                                          \
-      fprintf(stderr, "[ratsdf] group create failed: %s\n", #expr);      \
-      g->free_all();                                                     \
-      delete g;                                                          \
-      return RATSDF_ERR_DEVICE;                                          \
-    }                                                                    \
-  } while (0)
-  GROUP_CHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-  GROUP_CHK(g->d_engs.alloc((size_t)n * sizeof(EngineDev)));
-  for (int i = 0; i < 2; ++i) {
-    GROUP_CHK(g->h_engs[i].alloc((size_t)n * sizeof(EngineDev)));
-    GROUP_CHK(hipEventCreateWithFlags(&g->ev_stage[i], hipEventDisableTiming));
-  }
-  for (int i = 0; i < n; ++i)
-    GROUP_CHK(hipEventCreateWithFlags(&g->ev_member[(size_t)i], hipEventDisableTiming));
-  GROUP_CHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
-#undef GROUP_CHK
-  *out = g;
-  return RATSDF_OK;
-}
-
-int ratsdf_group_destroy(ratsdf_group* g) {
-  if (!g) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(g->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  g->free_all();
-  delete g;
-  return RATSDF_OK;
-}
-
-int ratsdf_group_size(ratsdf_group* g, int32_t* out) {
-  if (!g || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  *out = g->S;
-  return RATSDF_OK;
-}
-
-// Frame f of member s is element [f * S + s] of every array.
-int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* const* d_rgb,
-                                        const void* const* d_depth, const void* const* d_ht,
-                                        const void* const* d_lt, int height, int width,
-                                        float max_depth, const ratsdf_intrinsics* K,
-                                        const ratsdf_pose* T) {
-  if (!g || n < 0 || (n > 0 && (!d_rgb || !d_depth || !K || !T)) || height <= 0 || width <= 0)
-    return RATSDF_ERR_BAD_ARGUMENT;
-  if (n == 0) return RATSDF_OK;
-  const int S = g->S;
-  const size_t npix = (size_t)height * width;
-  for (size_t i = 0; i < (size_t)n * S; ++i)
-    if (!d_rgb[i] || !d_depth[i] || !finite_frame(K[i], T[i], max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(g->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  ratsdf_engine* e0 = g->eng[0];
-  if (npix * (size_t)e0->S >= 0xFFFFFFFFull) return RATSDF_ERR_BAD_ARGUMENT;
-  for (ratsdf_engine* e : g->eng) {
-    if (e->cand_ready) return RATSDF_ERR_BAD_ARGUMENT;  // cannot happen between complete calls
-    STCHK(e->ensure_image(npix, npix * (size_t)e->S));
-  }
-  // ---- tables ----
-  const unsigned slot = g->batch_no++ & 1u;
-  const size_t njobs = (size_t)n * S;
-  const size_t job_bytes = njobs * sizeof(FrameJob);
-  if (job_bytes > g->d_jobs.size() || job_bytes > g->h_jobs[0].size() || job_bytes > g->h_jobs[1].size()) {
-    HIPCHK(hipStreamSynchronize(g->stream));
-    STCHK(g->d_jobs.grow(job_bytes));
-    for (int i = 0; i < 2; ++i) STCHK(g->h_jobs[i].grow(job_bytes));
-  }
-  FrameJob* const d_jobs = g->d_jobs.as<FrameJob>();
-  EngineDev* const d_engs = g->d_engs.as<EngineDev>();
-  HIPCHK(hipEventSynchronize(g->ev_stage[slot]));  // the copy that last used this staging pair is done
-  for (int s = 0; s < S; ++s) g->h_engs[slot].as<EngineDev>()[s] = g->eng[(size_t)s]->record();
-  FrameJob* hj = g->h_jobs[slot].as<FrameJob>();
-  for (int f = 0; f < n; ++f)
-    for (int s = 0; s < S; ++s) {
-      const size_t i = (size_t)f * S + s;
-      const ratsdf_engine* e = g->eng[(size_t)s];
-      e->fill_job(hj[i], ratsdf_engine::FrameIn::at(i, d_rgb, d_depth, d_ht, d_lt, K, T), height, width, max_depth,
-                  e->parity + (unsigned)f);
-    }
-  // ---- ordering with the members' own streams (queries, single-engine frames) ----
-  for (int s = 0; s < S; ++s) {
-    HIPCHK(hipEventRecord(g->ev_member[(size_t)s], g->eng[(size_t)s]->stream));
-    HIPCHK(hipStreamWaitEvent(g->stream, g->ev_member[(size_t)s], 0));
-  }
-  HIPCHK(hipMemcpyAsync(d_engs, g->h_engs[slot].as<EngineDev>(), (size_t)S * sizeof(EngineDev),
-                        hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipMemcpyAsync(d_jobs, hj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipEventRecord(g->ev_stage[slot], g->stream));
-
-  // ---- launches ----
-  const bool fused = e0->fused_serial && e0->vpl != 1;
-  ratsdf_engine::Geom g1 = e0->geometry(height, width, true, e0->vpl == 1 ? 100 : g->split_a,
-                                        (fused || e0->vpl == 1) ? 0 : g->split_b);
-  ratsdf_engine::Geom g0 = e0->geometry(height, width, false, 0, 0);
-  // Several members at VGA-sized images: a member's slice of 1 536 update workgroups (two blocks each at 640x480 /
-  // 5 mm) instead of 4 096 -- a quarter of those are idle and still have to be dispatched, slice after slice
-  // (4 members, round 4: 46.3 k frames/s at 4 096, 47.1 k at 3 072, 48.0 k at 2 048, 48.9 k at 1 536 and 1 024;
-  // a single stream measures the same from 1 536 to 4 096)
-  if (!e0->grid_from_env && S >= 2 && g0.grid == 4096u) g0.grid = g1.grid = 1536u;
-  const unsigned grid0 = g0.grid;
-  const uint32_t commit_rot = fused ? e0->commit_rotation(grid0, grid0 * (unsigned)S) : 0u;
-  // events for every frame that will be timed: created before anything is launched
-  if (g->timer.on) STCHK(g->timer.reserve((size_t)n / 4 + 2));
-  // A failure from here on leaves launches queued on the group's stream on behalf of members that do
-  // not know about them: the members are brought to a consistent state before the error is returned.
-  auto abandon = [&](int frames_launched) {
-    (void)hipStreamSynchronize(g->stream);
-    for (ratsdf_engine* e : g->eng) e->abandon_pipeline(frames_launched, true);
-  };
-  const Enqueued q = enqueue_jobs(g->stream, (EnginePtr)d_engs, d_jobs, n, S, g0, g1, commit_rot, fused ? 8u : 0u,
-                                  (e0->tab.tail_on ? 1u : 0u) | e0->front_prio, e0->vpl, &g->timer);
-  if (q.status != RATSDF_OK) {
-    abandon(q.frames);
-    return q.status;
-  }
-  if (hipEventRecord(g->ev_done, g->stream) != hipSuccess) {
-    abandon(n);
-    return RATSDF_ERR_DEVICE;
-  }
-  int st_all = RATSDF_OK;
-  for (ratsdf_engine* e : g->eng) {
-    if (hipStreamWaitEvent(e->stream, g->ev_done, 0) != hipSuccess) st_all = RATSDF_ERR_DEVICE;
-    e->parity = (e->parity + (unsigned)n) & 1u;
-    e->cand_ready = false;
-    e->pending = true;
-  }
-  if (st_all != RATSDF_OK) (void)hipStreamSynchronize(g->stream);  // ordering by waiting instead
-  return st_all;
-}
-
-int ratsdf_group_synchronize(ratsdf_group* g) {
-  if (!g) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(g->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  HIPCHK(hipStreamSynchronize(g->stream));
-  int worst = RATSDF_OK;
-  for (ratsdf_engine* e : g->eng) {
-    const int st = ratsdf_synchronize(e);
-    if (st != RATSDF_OK && worst == RATSDF_OK) worst = st;
-  }
-  return worst;
-}
-
-int ratsdf_group_profile_enable(ratsdf_group* g, int enable) {
-  if (!g) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(g->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  const int st = g->timer.drain(g->stream);
-  g->timer.on = enable != 0;
-  return st;
-}
-
-int ratsdf_group_profile_read(ratsdf_group* g, double* ms, int64_t* launches) {
-  if (!g) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(g->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  return g->timer.read(g->stream, ms, launches);
-}
-
-}  // extern "C"
-
+// Above: creation, the integrate family, synchronise, recover, profile and the counters.  The other entry-point
+// families, one file each (this stays ONE translation unit: the files need the engine record, the
+// macros and the helpers above, and the order of the kernels is the order of the headers and of mapfile.inc).
+#include "debug.inc"    // ratsdf_debug_*: readers of the diagnostic build's stamps and counters
+#include "query.inc"    // ratsdf_query / ratsdf_gather_valid* / ratsdf_download_all* / ratsdf_raycast*
+#include "sample.inc"   // ratsdf_sample_points[_device] (include/ratsdf_sample.h)
+#include "esdf.inc"     // ratsdf_esdf[_device] (include/ratsdf_esdf.h)
+#include "blocks.inc"   // directory export and delta, block import / export, ratsdf_test_*, ratsdf_dump_*
+#include "group.inc"    // ratsdf_group_*: several engines of one device stepped together
 #include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)
 #include "fuse.inc"     // ratsdf_fuse_map / ratsdf_fuse_blocks[_device] / ratsdf_fuse_map_file (include/ratsdf_fuse.h)
