@@ -23,6 +23,7 @@
 #include "kernels_sample.h"
 #include "kernels_esdf.h"
 #include "kernels_fuse.h"
+#include "kernels_resample.h"
 #include "hip_mem.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
@@ -1949,3 +1950,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "group.inc"    // ratsdf_group_*: several engines of one device stepped together
 #include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)
 #include "fuse.inc"     // ratsdf_fuse_map / ratsdf_fuse_blocks[_device] / ratsdf_fuse_map_file (include/ratsdf_fuse.h)
+#include "resample.inc" // ratsdf_resample_blocks_device / ratsdf_fuse_map_transformed (include/ratsdf_resample.h)

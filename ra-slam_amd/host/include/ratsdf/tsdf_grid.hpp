@@ -52,6 +52,8 @@ struct Api {
   int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
                      ratsdf_fuse_stats*) = nullptr;
   int (*fuse_map_file)(ratsdf_engine*, const char*, ratsdf_fuse_stats*) = nullptr;
+  // include/ratsdf_resample.h: likewise optional
+  int (*fuse_map_transformed)(ratsdf_engine*, ratsdf_engine*, const ratsdf_pose*, ratsdf_fuse_stats*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -118,6 +120,9 @@ class TSDFGrid {
   int FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw, const float* prob,
                  ratsdf_fuse_stats* stats = nullptr);
   int FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats = nullptr);
+  // transformed map fusion (include/ratsdf_resample.h): another grid's map resampled onto this grid's lattice under
+  // dst_T_src (p_dst = R(q) p_src + t, metres: a map-to-map pose, not a camera pose) and fused.  Return the status.
+  int FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats = nullptr);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

@@ -154,6 +154,7 @@ class TSDFSystem {
   int FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw, const float* prob,
                  ratsdf_fuse_stats* stats = nullptr);
   int FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats = nullptr);
+  int FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats = nullptr);
   // TSDFGrid::ESDF under the engine's mutex, like Sample
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);

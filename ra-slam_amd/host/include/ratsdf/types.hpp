@@ -16,6 +16,7 @@
 #include "../../../../include/ratsdf_map.h"
 #include "../../../../include/ratsdf_sample.h"
 #include "../../../../include/ratsdf_fuse.h"
+#include "../../../../include/ratsdf_resample.h"
 #include "../../../../include/ratsdf_esdf.h"
 
 namespace ratsdf {

@@ -81,6 +81,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.fuse_map = reinterpret_cast<decltype(api.fuse_map)>(opt_sym("fuse_map"));
   api.fuse_blocks = reinterpret_cast<decltype(api.fuse_blocks)>(opt_sym("fuse_blocks"));
   api.fuse_map_file = reinterpret_cast<decltype(api.fuse_map_file)>(opt_sym("fuse_map_file"));
+  api.fuse_map_transformed = reinterpret_cast<decltype(api.fuse_map_transformed)>(opt_sym("fuse_map_transformed"));
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   return loaded.emplace(key, api).first->second;
 }
@@ -251,6 +252,14 @@ int TSDFGrid::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
   if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   note(api_->fuse_map_file ? api_->fuse_map_file(engine_, path.c_str(), stats) : RATSDF_ERR_NOT_IMPLEMENTED,
        "FuseMapFile");
+  return status_;
+}
+
+int TSDFGrid::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats) {
+  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->fuse_map_transformed ? api_->fuse_map_transformed(engine_, src.engine_, &dst_T_src, stats)
+                                  : RATSDF_ERR_NOT_IMPLEMENTED,
+       "FuseMapTransformed");
   return status_;
 }
 
@@ -538,6 +547,12 @@ int TSDFSystem::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
   Flush();
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.FuseMapFile(path, stats);
+}
+
+int TSDFSystem::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.FuseMapTransformed(src, dst_T_src, stats);
 }
 
 int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {

@@ -98,6 +98,8 @@ FUSE_SYMBOLS = ["fuse_map", "fuse_blocks", "fuse_blocks_device", "fuse_map_file"
 FUSE_STATS = np.dtype([("blocks_seen", "<i8"), ("blocks_allocated", "<i8"), ("blocks_skipped", "<i8"),
                        ("voxels_copied", "<i8"), ("voxels_averaged", "<i8")])
 assert FUSE_STATS.itemsize == 40
+# include/ratsdf_resample.h (transformed map fusion): handled like FUSE_SYMBOLS
+RESAMPLE_SYMBOLS = ["resample_blocks_device", "fuse_map_transformed"]
 ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
 
 
@@ -240,6 +242,15 @@ class Library:
                 f.argtypes = {"fuse_map": [vp, vp, vp], "fuse_blocks": [vp, C.c_int32, vp, vp, vp, vp, vp],
                               "fuse_blocks_device": [vp, C.c_int32, vp, vp, vp],
                               "fuse_map_file": [vp, C.c_char_p, vp]}[s]
+            self.fn[s] = f
+        for s in RESAMPLE_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = {"resample_blocks_device": [vp, C.POINTER(Pose), C.c_int32, vp, vp, vp],
+                              "fuse_map_transformed": [vp, vp, C.POINTER(Pose), vp]}[s]
             self.fn[s] = f
 
     def backend(self):
@@ -697,6 +708,22 @@ class Engine:
     def fuse_map_file(self, path):
         """fuses a checkpoint written by save_map() into this map (only voxel size and truncation must agree)"""
         return self._fuse("fuse_map_file", os.fsencode(path))
+
+    # -- transformed map fusion (include/ratsdf_resample.h) --------------------------------
+    def fuse_map_transformed(self, src, dst_T_src):
+        """resamples the map of ``src`` onto this map's lattice under ``dst_T_src`` (qx, qy, qz, qw, tx, ty, tz as
+        ratsdf.pose builds it: p_dst = R(q) p_src + t in metres, a map-to-map pose) and fuses it; ``src`` is only
+        read.  Returns the statistics (raises like the other fusion calls)."""
+        p = _as_pose(dst_T_src)
+        return self._fuse("fuse_map_transformed", src._h, C.byref(p))
+
+    def resample_blocks_device(self, dst_T_src, n, d_block_pos, d_voxels, d_contrib=0):
+        """blocks of the DESTINATION lattice (d_block_pos: n x 3 int16) filled from this map seen through
+        ``dst_T_src``: d_voxels gets n records in export_blocks_device()'s layout, d_contrib (or 0) one int32 per
+        block, the number of contributing voxels.  Device pointers; asynchronous on this engine's stream."""
+        p = _as_pose(dst_T_src)
+        _check(self.lib.fn["resample_blocks_device"](self._h, C.byref(p), int(n), d_block_pos or None,
+                                                     d_voxels or None, d_contrib or None), "resample_blocks_device")
 
     # -- test hooks ------------------------------------------------------------------------
     @staticmethod
