@@ -22,11 +22,13 @@
 #include "kernels_mesh.h"
 #include "kernels_sample.h"
 #include "kernels_esdf.h"
+#include "kernels_surface.h"
 #include "kernels_fuse.h"
 #include "kernels_resample.h"
 #include "hip_mem.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
+#include "../../include/ratsdf_surface.h"
 
 static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
 
@@ -239,6 +241,10 @@ struct EngineMem {
   HostMem h_sample;
   DevMem d_esdf;       // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks (ratsdf_engine::esdf_cap)
   HostMem h_esdf;      // page-locked copy of the host entry point's results, passed through in chunks
+  DevMem d_surface;    // surface-point workspace (ratsdf_surface_points*): counts | starts | tile sums | total
+                       // (ratsdf_engine::surface_cap)
+  DevMem d_surface_pts;  // the host entry point's records on the device, and their page-locked pass-through
+  HostMem h_surface;
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
@@ -348,6 +354,7 @@ struct ratsdf_engine : EngineMem {
   ratsdf_frame_stats* d_stats = nullptr;
   int grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes);
   size_t esdf_cap = 0;        // voxels the ESDF workspace was laid out for
+  size_t surface_cap = 0;     // cells of the block grid the surface-point workspace was laid out for
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
   EngineDev* d_eng = nullptr;  // device copy of the engine record (device_types.h)
 
@@ -1296,7 +1303,7 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
 }
 
 // a sticky error some finished launch has already raised, without waiting for the stream (ratsdf_engine::sticky): the
-// check of the asynchronous entry points of sample.inc and esdf.inc
+// check of the asynchronous entry points of sample.inc, esdf.inc and surface.inc
 static int sticky_raised(ratsdf_engine* e) {
   return *(volatile uint32_t*)e->h_err != 0u ? e->sticky() : RATSDF_OK;
 }
@@ -1946,6 +1953,7 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "query.inc"    // ratsdf_query / ratsdf_gather_valid* / ratsdf_download_all* / ratsdf_raycast*
 #include "sample.inc"   // ratsdf_sample_points[_device] (include/ratsdf_sample.h)
 #include "esdf.inc"     // ratsdf_esdf[_device] (include/ratsdf_esdf.h)
+#include "surface.inc"  // ratsdf_surface_points[_device] (include/ratsdf_surface.h)
 #include "blocks.inc"   // directory export and delta, block import / export, ratsdf_test_*, ratsdf_dump_*
 #include "group.inc"    // ratsdf_group_*: several engines of one device stepped together
 #include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)

@@ -47,6 +47,9 @@ struct Api {
   int (*sample_points)(ratsdf_engine*, const float*, size_t, ratsdf_sample*) = nullptr;
   // include/ratsdf_esdf.h: likewise optional (not in the CPU oracle)
   int (*esdf)(ratsdf_engine*, const int32_t*, const int32_t*, float, uint32_t, float*, uint8_t*) = nullptr;
+  // include/ratsdf_surface.h: likewise optional (not in the CPU oracle)
+  int (*surface_points)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_surface_params*,
+                        ratsdf_surface_point**, size_t*) = nullptr;
   // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
   int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
   int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
@@ -113,6 +116,11 @@ class TSDFGrid {
   // (also kept in last_status()); no reference counterpart.
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);
+  // oriented surface points of a box of voxels (include/ratsdf_surface.h): every sign change of the TSDF between two
+  // neighbouring voxels as position, normal into free space, probability, colour and weight, in the header's order.
+  // Returns the status (also kept in last_status()); *out is empty unless it is RATSDF_OK.  No reference counterpart.
+  int SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
+                    std::vector<ratsdf_surface_point>* out);
   // map fusion (include/ratsdf_fuse.h): another grid's map (same device, voxel size and truncation; only read), n
   // blocks in ratsdf_import_blocks' layout, or a checkpoint file merged into this map with the weighted-average voxel
   // update.  stats may be nullptr.  Return the status (also kept in last_status()); no reference counterpart.

@@ -158,6 +158,9 @@ class TSDFSystem {
   // TSDFGrid::ESDF under the engine's mutex, like Sample
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);
+  // TSDFGrid::SurfacePoints under the engine's mutex, like Sample
+  int SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
+                    std::vector<ratsdf_surface_point>* out);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

@@ -18,6 +18,7 @@
 #include "../../../../include/ratsdf_fuse.h"
 #include "../../../../include/ratsdf_resample.h"
 #include "../../../../include/ratsdf_esdf.h"
+#include "../../../../include/ratsdf_surface.h"
 
 namespace ratsdf {
 

@@ -20,13 +20,19 @@
 //          [--load-map FILE (a map checkpoint to continue, before the first frame; its voxel size must be --voxel)]
 //          [--first-frame K (skip the first K frames of the dataset)] [--save-map FILE (after the last frame)]
 //          [--fuse-map FILE (a checkpoint fused into the map after the last frame, before --save-map / the downloads)]
+//          [--surface-points FILE (after the last frame: the oriented surface points of the map's bounding box,
+//          32-byte records of include/ratsdf_surface.h, min_weight 1; a box beyond 512 voxels along an axis is
+//          covered by block-aligned boxes of at most 512, z then y then x, each in the header's order)]
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "ratsdf/dataset.hpp"
 #include "ratsdf/tsdf_system.hpp"
@@ -42,6 +48,37 @@ void write_file(const std::string& path, const void* data, size_t bytes) {
     exit(2);
   }
 }
+
+// the oriented surface points of the map's bounding box (include/ratsdf_surface.h) as a file of records
+int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
+  const float far = 32000.f * vs;  // (every voxel index the directory can hold lies within +-32768)
+  const std::vector<VoxelSpatialTSDF> vox = tsdf.Query(BoundingCube<float>{-far, far, -far, far, -far, far});
+  std::vector<ratsdf_surface_point> all, part;
+  if (!vox.empty()) {
+    int lo[3] = {32767, 32767, 32767}, hi[3] = {-32768, -32768, -32768};
+    for (const VoxelSpatialTSDF& v : vox) {
+      const int idx[3] = {(int)lrintf(v.x / vs), (int)lrintf(v.y / vs), (int)lrintf(v.z / vs)};
+      for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], idx[a]), hi[a] = std::max(hi[a], idx[a]);
+    }
+    for (int a = 0; a < 3; ++a) lo[a] = std::max(lo[a] & ~7, -32768), hi[a] = std::min(hi[a] | 7, 32767);  // whole blocks
+    ratsdf_surface_params params;
+    memset(&params, 0, sizeof(params));
+    params.min_weight = 1;
+    for (int z = lo[2]; z <= hi[2]; z += 512)
+      for (int y = lo[1]; y <= hi[1]; y += 512)
+        for (int x = lo[0]; x <= hi[0]; x += 512) {
+          const int32_t origin[3] = {x, y, z};
+          const int32_t dims[3] = {std::min(512, hi[0] - x + 1), std::min(512, hi[1] - y + 1),
+                                   std::min(512, hi[2] - z + 1)};
+          const int st = tsdf.SurfacePoints(origin, dims, params, &part);
+          if (st != RATSDF_OK) return st;
+          all.insert(all.end(), part.begin(), part.end());
+        }
+  }
+  write_file(path, all.data(), all.size() * sizeof(ratsdf_surface_point));
+  fprintf(stderr, "[offline_eval] %zu surface points to %s\n", all.size(), path.c_str());
+  return RATSDF_OK;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -53,7 +90,7 @@ int main(int argc, char** argv) {
   const char* lib = nullptr;
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
-  std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map;
+  std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -78,6 +115,7 @@ int main(int argc, char** argv) {
     else if (a == "--load-map") load_map = next();
     else if (a == "--save-map") save_map = next();
     else if (a == "--fuse-map") fuse_map = next();
+    else if (a == "--surface-points") surface_points = next();
     else if (a == "--first-frame") first_frame = atoi(next());
     else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -185,6 +223,14 @@ int main(int argc, char** argv) {
       if (!download_mesh.empty())  // offline_eval.cc:95-98
         tsdf->DownloadAllMesh(download_mesh + "_vertices.bin", download_mesh + "_indices.bin",
                               download_mesh + "_vertices_prob.bin");
+      if (!surface_points.empty()) {
+        const int st = write_surface_points(*tsdf, voxel_size, surface_points);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --surface-points %s: %s\n", surface_points.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
       tsdf->terminate();
     } else {
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();

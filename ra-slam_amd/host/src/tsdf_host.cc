@@ -83,6 +83,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.fuse_map_file = reinterpret_cast<decltype(api.fuse_map_file)>(opt_sym("fuse_map_file"));
   api.fuse_map_transformed = reinterpret_cast<decltype(api.fuse_map_transformed)>(opt_sym("fuse_map_transformed"));
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
+  api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -268,6 +269,22 @@ int TSDFGrid::ESDF(const int32_t origin[3], const int32_t dims[3], float occupie
   if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   note(api_->esdf ? api_->esdf(engine_, origin, dims, occupied_below, flags, out, state) : RATSDF_ERR_NOT_IMPLEMENTED,
        "ESDF");
+  return status_;
+}
+
+int TSDFGrid::SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
+                            std::vector<ratsdf_surface_point>* out) {
+  if (out) out->clear();
+  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_surface_point* buf = nullptr;
+  size_t n = 0;
+  note(api_->surface_points ? api_->surface_points(engine_, origin, dims, &params, &buf, &n)
+                            : RATSDF_ERR_NOT_IMPLEMENTED,
+       "SurfacePoints");
+  if (status_ == RATSDF_OK && buf) {
+    out->assign(buf, buf + n);
+    api_->free_buffer(buf);
+  }
   return status_;
 }
 
@@ -564,6 +581,12 @@ int TSDFSystem::ESDF(const int32_t origin[3], const int32_t dims[3], float occup
                      uint8_t* state) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.ESDF(origin, dims, occupied_below, flags, out, state);
+}
+
+int TSDFSystem::SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
+                              std::vector<ratsdf_surface_point>* out) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.SurfacePoints(origin, dims, params, out);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

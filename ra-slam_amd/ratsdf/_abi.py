@@ -101,6 +101,16 @@ assert FUSE_STATS.itemsize == 40
 # include/ratsdf_resample.h (transformed map fusion): handled like FUSE_SYMBOLS
 RESAMPLE_SYMBOLS = ["resample_blocks_device", "fuse_map_transformed"]
 ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
+# include/ratsdf_surface.h (oriented surface points of a box): handled like ESDF_SYMBOLS
+SURFACE_SYMBOLS = ["surface_points", "surface_points_device"]
+# ratsdf_surface_point (32 bytes)
+SURFACE_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("prob", "<f4"), ("rgbw", RGBW_DTYPE)])
+assert SURFACE_DTYPE.itemsize == 32
+
+
+class SurfaceParams(C.Structure):
+    """ratsdf_surface_params"""
+    _fields_ = [("min_weight", C.c_int32), ("min_prob", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class _OwnedBuffer:
@@ -231,6 +241,16 @@ class Library:
             else:
                 f.restype = C.c_int
                 f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_uint32, vp, vp]
+            self.fn[s] = f
+        for s in SURFACE_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(SurfaceParams)]
+                f.argtypes = box + {"surface_points": [C.POINTER(vp), C.POINTER(C.c_size_t)],
+                                    "surface_points_device": [vp, C.c_int64, vp]}[s]
             self.fn[s] = f
 
         for s in FUSE_SYMBOLS:
@@ -626,6 +646,35 @@ class Engine:
         _check(self.lib.fn["esdf_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
                                           C.c_float(occupied_below), _esdf_flags(unknown_occupied), d_out or None,
                                           d_state or None), "esdf_device")
+
+    def surface_points(self, origin, dims, min_weight=1, min_prob=0.0):
+        """oriented surface points of a box of voxels (ratsdf_surface_points, include/ratsdf_surface.h): origin is the
+        voxel index of the box's minimum corner, dims the voxels per axis (voxel_box turns a metric box into them).
+        Returns SURFACE_DTYPE records -- position in metres, unit normal into free space, probability, colour and
+        weight of the nearer voxel -- of every sign change of the TSDF between two neighbouring voxels of at least
+        min_weight, in block order (z, y, x), then voxel order within the block, then axis."""
+        p, n = C.c_void_p(), C.c_size_t()
+        params = SurfaceParams(int(min_weight), float(min_prob), 0, 0)
+        _check(self.lib.fn["surface_points"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                             C.byref(p), C.byref(n)), "surface_points")
+        return self._take(p, n.value, SURFACE_DTYPE)
+
+    def surface_points_device(self, origin, dims, d_points, capacity, d_count, min_weight=1, min_prob=0.0):
+        """surface_points() into DEVICE buffers, asynchronous on the engine's stream: the first min(total, capacity)
+        32-byte records to d_points (16-byte aligned; 0 with capacity 0 for a pure count) and the total as an int64 to
+        d_count.  d_points / d_count: a torch tensor, a devmem.DeviceArray or a raw pointer.  Returns the total (this
+        waits for the stream)."""
+        params = SurfaceParams(int(min_weight), float(min_prob), 0, 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_points, d_count)]
+        _check(self.lib.fn["surface_points_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
+                                                    C.byref(params), ptr[0] or None, int(capacity), ptr[1] or None),
+               "surface_points_device")
+        self.synchronize()
+        if hasattr(d_count, "cpu"):          # a torch tensor
+            return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
+        if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
+            return int(d_count.numpy().view(np.int64).reshape(-1)[0])
+        return None                          # a raw pointer: the caller reads it
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Timings of the query-side entry points on the bench map, HIP engine vs
-the CPU oracle (16 threads): tools/aux_bench.py  (GPU box)"""
+the CPU oracle (16 threads): tools/aux_bench.py  (GPU box).  The last leg times the surface points
+(include/ratsdf_surface.h) beside the mesh export and the host route on the same map; `--surface` runs that leg and
+the mesh export alone (no oracle)."""
 import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -14,10 +16,11 @@ from oracle_binding import load_oracle
 
 vs, md = 0.005, 4.0
 gpu = ratsdf.TSDFGrid(vs, 6 * vs)
-cpu = Engine(load_oracle(), vs, 6 * vs, threads=16)
+only_surface = "--surface" in sys.argv
+cpu = None if only_surface else Engine(load_oracle(), vs, 6 * vs, threads=16)
 frames = [synthetic.frame("room", i, noise=True, holes=True) for i in range(45)]
 for f in frames:
-    for e in (gpu, cpu):
+    for e in (gpu, cpu) if cpu else (gpu,):
         e.integrate(f["rgb"], f["depth"], f["ht"], f["lt"], md, f["intrinsics"], f["pose"])
 print("map:", gpu.num_active_blocks(), "blocks")
 
@@ -34,13 +37,58 @@ rows = []
 for name, g, c, reps in [
     ("raycast 640x480 (host images out)", lambda: gpu.raycast(f["intrinsics"], H, W, f["pose"], 2 * md),
      lambda: cpu.raycast(f["intrinsics"], H, W, f["pose"], 2 * md), 20),
-    ("gather_valid (16-B records)", gpu.gather_valid, cpu.gather_valid, 5),
-    ("gather_valid_semantic (20-B records)", gpu.gather_valid_semantic, cpu.gather_valid_semantic, 5),
+    ("gather_valid (16-B records)", gpu.gather_valid, cpu and cpu.gather_valid, 5),
+    ("gather_valid_semantic (20-B records)", gpu.gather_valid_semantic, cpu and cpu.gather_valid_semantic, 5),
     ("query, 1 m cube", lambda: gpu.query((-0.5, 0.5, -0.5, 0.5, 1.0, 2.0)), lambda: cpu.query((-0.5, 0.5, -0.5, 0.5, 1.0, 2.0)), 10),
-    ("gather_valid_mesh (marching cubes)", gpu.gather_valid_mesh, cpu.gather_valid_mesh, 3),
-]:
+    ("gather_valid_mesh (marching cubes)", gpu.gather_valid_mesh, cpu and cpu.gather_valid_mesh, 3),
+][4 if only_surface else 0:]:
     tg, rg = timed(g, reps)
-    tc, rc = timed(c, max(1, reps // 3))
+    tc, rc = timed(c, max(1, reps // 3)) if cpu else (float("nan"), None)
     n = len(rg[0]) if isinstance(rg, tuple) else len(rg)
     rows.append((name, tg * 1e3, tc * 1e3, n))
     print(f"{name:40s} HIP {tg * 1e3:8.2f} ms   CPU-16T oracle {tc * 1e3:9.2f} ms   ({n} items)")
+
+# ---- surface points of the map's bounding box and of a 128^3 box, beside the mesh export above and the host route ----
+from ratsdf import devmem
+_, blocks = gpu.dump_directory()
+pos = np.stack([blocks["x"], blocks["y"], blocks["z"]], axis=1).astype(int)
+lo, hi = pos.min(0) * 8, pos.max(0) * 8 + 7
+# the entry point takes at most 2^27 voxels and 1024 per axis: block-aligned boxes of at most 512 cover the rest
+tiles = [([x, y, z], [min(512, hi[0] - x + 1), min(512, hi[1] - y + 1), min(512, hi[2] - z + 1)])
+         for z in range(lo[2], hi[2] + 1, 512) for y in range(lo[1], hi[1] + 1, 512) for x in range(lo[0], hi[0] + 1, 512)]
+d_cnt = devmem.DeviceArray(np.zeros(1, dtype=np.int64))
+total = sum(gpu.surface_points_device(o, d, 0, 0, d_cnt) for o, d in tiles)
+d_pts = devmem.DeviceArray(np.zeros((total + 1, 8), dtype=np.int32))
+
+
+def whole_box():
+    n = 0
+    for o, d in tiles:      # (each call returns after a synchronise: the time is the kernels', not the enqueue's)
+        n += gpu.surface_points_device(o, d, d_pts.data_ptr() + 32 * n, total - n, d_cnt)
+    return n
+
+
+mid = (lo + hi + 1) // 2 // 8 * 8
+cube = ([int(v) - 64 for v in mid], [128, 128, 128])
+in_cube = int(np.all((pos * 8 >= np.array(cube[0]) - 7) & (pos * 8 < np.array(cube[0]) + 128), axis=1).sum())
+
+
+def host_route():
+    """every voxel of the map to the host, then a numpy sign-change search inside each block (edges across block
+    seams, the observed rule, normals and compaction are not even attempted: a lower bound of the host route)"""
+    rec = gpu.gather_valid_semantic()
+    t = rec["tsdf"].reshape(-1, 8, 8, 8)
+    neg = t < 0
+    return int((neg[:, :, :, 1:] != neg[:, :, :, :-1]).sum() + (neg[:, :, 1:] != neg[:, :, :-1]).sum() +
+               (neg[:, 1:] != neg[:, :-1]).sum())
+
+
+t_box, n_box = timed(whole_box, 10)
+t_cube, n_cube = timed(lambda: gpu.surface_points_device(*cube, d_pts, total, d_cnt), 20)
+t_host, n_host = timed(host_route, 3)
+t_mesh = rows[-1][1]
+print(f"surface points: map of {len(pos)} blocks, bounding box {[int(v) for v in hi - lo + 1]} voxels in {len(tiles)} call(s)")
+print(f"  surface_points_device, bounding box   {t_box * 1e3:8.2f} ms   ({n_box} points)")
+print(f"  surface_points_device, 128^3 box      {t_cube * 1e3:8.2f} ms   ({n_cube} points, {in_cube} blocks in the box)")
+print(f"  gather_valid_mesh (from above)        {t_mesh:8.2f} ms")
+print(f"  host route (gather_valid_semantic + numpy sign changes inside blocks) {t_host * 1e3:8.2f} ms   ({n_host} changes)")
