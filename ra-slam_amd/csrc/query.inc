@@ -13,6 +13,9 @@ static int ensure_download_buffers(ratsdf_engine* e, size_t bytes) {
 static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t* n) {
   uint32_t cnt = 0;
   STCHK(e->read_small(&cnt, &e->ctl->n_sel, 4));
+  // (the read waited for the stream: a device error of an earlier frame is known by now, and ratsdf.h has every
+  // query report it -- the records of a map that lost a frame's blocks must not pass for the map)
+  STCHK(sticky_raised(e));
   const size_t rec = semantic ? sizeof(ratsdf_voxel_segm) : sizeof(ratsdf_voxel_tsdf);
   const size_t total = (size_t)cnt * RATSDF_BLOCK_VOLUME;
   void* host = malloc(total ? total * rec : 1);
