@@ -37,7 +37,10 @@ def mirrored_tsdf(g, corner):
     return t0 * ax + t1 * (F(1) - ax)
 
 
-def sample(points, vs, lookup):
+def sample(points, vs, lookup, floor=np.floor, nearest=None, guard=True):
+    """the contract.  floor / nearest / guard exist so that a test can state a WRONG variant (trunc for floor, another
+    rounding for roundf, no range guard: the corners then wrap to int16) and show that its cases tell it apart"""
+    nearest = round_half_away if nearest is None else nearest
     p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
     n = p.shape[0]
     vs = F(vs)
@@ -46,19 +49,23 @@ def sample(points, vs, lookup):
     out["grad"] = QNAN
     with np.errstate(invalid="ignore", over="ignore"):
         g = p / vs
-        l = np.floor(g)
+        l = floor(g)
         ok = np.all((l >= F(-32768)) & (l <= F(32766)), axis=1)  # NaN fails every comparison
+        if not guard:
+            ok = np.all(np.isfinite(l) & (np.abs(l) < F(2 ** 31)), axis=1)
     if not ok.any():
         return out
     g, l = g[ok], l[ok]
     f = g - l
     u = F(1) - f
     li = l.astype(np.int64)
-    near = (round_half_away(g) != l).astype(np.int64)  # 0: floor, 1: floor + 1
+    near = (nearest(g) != l).astype(np.int64)  # 0: floor, 1: floor + 1
     m = g.shape[0]
     corners = np.empty((8, m, 3), dtype=np.int64)
     for k in range(8):
         corners[k] = li + np.array([k >> 2, (k >> 1) & 1, k & 1])
+    if not guard:
+        corners = ((corners + 32768) & 0xFFFF) - 32768
     alloc, tsdf, rgbw, prob = lookup(corners.reshape(-1, 3))
     alloc = np.asarray(alloc, dtype=bool).reshape(8, m)
     t = np.asarray(tsdf, dtype=np.float32).reshape(8, m)
