@@ -109,7 +109,7 @@ typedef struct ratsdf_config {
   int32_t bucket_bits;  /* 0 -> RATSDF_DEFAULT_BUCKET_BITS */
   /* Block-ownership sharding across GPUs (no reference counterpart): a candidate block
    * is inserted only if owner(block) == shard_rank, owner = floormod(x >> shard_slab_bits, count).
-   * shard_count <= 1 disables the filter. */
+   * shard_count <= 1 disables the filter.  shard_slab_bits <= 0 -> 2 (slabs of four blocks), as block_bits 0. */
   int32_t shard_rank;
   int32_t shard_count;
   int32_t shard_slab_bits;

@@ -25,7 +25,9 @@
  *
  * tsdf, colour and weight are exact.  The probability is the log-odds form the frame update uses (weighted geometric
  * pooling of p and 1 - p, voxel_tsdf.cu:242-248) on the hardware's log / exp / reciprocal: within 1e-4 of the line
- * above evaluated in fp32, NaN exactly where that is NaN (p = 0 on one side and p = 1 on the other).
+ * above evaluated in fp32, NaN exactly where that is NaN (p = 0 on one side and p = 1 on the other).  That holds for
+ * every float a map can carry, a probability below FLT_MIN included: the hardware's log2 reads a subnormal input as
+ * zero, so the odds of such a voxel are scaled into the normal range before their logarithm is taken.
  *
  * What fusion is NOT: it is not equal to integrating all frames of both maps into one map.  Each map carries the fresh
  * voxel's prior (weight 1, tsdf -1) in its averages, weights are rounded to bytes and capped at 40 in each map before
@@ -39,8 +41,11 @@
  * can lose its bucket to another one of the same pass, so a call makes up to 8 allocation passes per chunk of blocks; a
  * block is fused exactly once, in the first pass that finds it.  Blocks that still have no place after 8 passes:
  * RATSDF_ERR_CAPACITY -- as after every error but RATSDF_ERR_BAD_ARGUMENT, the blocks already fused STAY fused (there
- * is no un-fusing), and *stats says how far the call got.  n == 0 is RATSDF_OK and launches nothing; an empty source
- * is RATSDF_OK and leaves the destination as it is (only the source's directory is looked at).
+ * is no un-fusing), and *stats says how far the call got.  This RATSDF_ERR_CAPACITY is the call's own status, not a
+ * sticky engine error: ratsdf_synchronize reports nothing afterwards, the engine stays usable, and the blocks that
+ * found no place (the listed positions the directory still lacks) may be offered again.  n == 0 is RATSDF_OK and
+ * launches nothing; an empty source is RATSDF_OK and leaves the destination as it is (only the source's directory is
+ * looked at).
  * Every call returns when the fusion is done (it synchronises the engine's stream).
  */
 #ifndef RATSDF_FUSE_H_

@@ -59,6 +59,17 @@ __device__ inline bool fuse_contributes(uint32_t rgbw, uint32_t tsdf_bits) {
   return w != 0u && !(w == 1u && tsdf_bits == 0xBF800000u);
 }
 
+// log2 of the odds p / (1 - p).  The hardware's log2 reads a subnormal input as zero (-inf where the header's logf
+// gives -88 .. -103), and a probability below 2^-126 has subnormal odds: those are scaled into the normal range first,
+// as the compiler's own log2 lowering does.  Every other input -- normal, zero, negative, infinite, NaN -- takes the one
+// instruction it always took.  (A branch that no wave of a scanned map takes; the select form of the same costs the
+// kernel two registers and with them a wave per SIMD.)
+__device__ inline float fuse_log2_odds(float o) {
+  float l = __builtin_amdgcn_logf(o);
+  if (__builtin_expect(o < 0x1p-126f && o > 0.f, 0)) l = __builtin_amdgcn_logf(o * 0x1p32f) - 32.f;
+  return l;
+}
+
 // One voxel.  Returns 0: unchanged, 1: copied, 2: averaged.
 __device__ inline uint32_t fuse_voxel(uint32_t& at, uint32_t& ac, uint32_t& ap, uint32_t bt, uint32_t bc, uint32_t bp) {
   if (!fuse_contributes(bc, bt)) return 0u;
@@ -79,8 +90,8 @@ __device__ inline uint32_t fuse_voxel(uint32_t& at, uint32_t& ac, uint32_t& ap, 
   const uint32_t w = (uint32_t)fminf(wc, 40.f);
   // probability: the log-odds form of the frame update (kernels_integrate.h), hardware log2 / exp2 / rcp
   const float pa = __uint_as_float(ap), pb = __uint_as_float(bp);
-  const float la = __builtin_amdgcn_logf(pa * __builtin_amdgcn_rcpf(1.f - pa)) * 0.69314718f;
-  const float lb = __builtin_amdgcn_logf(pb * __builtin_amdgcn_rcpf(1.f - pb)) * 0.69314718f;
+  const float la = fuse_log2_odds(pa * __builtin_amdgcn_rcpf(1.f - pa)) * 0.69314718f;
+  const float lb = fuse_log2_odds(pb * __builtin_amdgcn_rcpf(1.f - pb)) * 0.69314718f;
   const float x = (wa * la + wb * lb) * rwc.r1;
   const float ex = __builtin_amdgcn_exp2f(x * -1.44269504f);
   at = __float_as_uint(t);

@@ -132,9 +132,11 @@ def fuse(dst, src, shard=None):
     return (pos, t, c, p), info
 
 
-def assert_sets_match(got, want, colour_known=None, prob_tol=1e-4, what="", tsdf_tol=None):
+def assert_sets_match(got, want, colour_known=None, prob_tol=1e-4, what="", tsdf_tol=None, tsdf_nan_payload=True):
     """block sets equal by position: block set, tsdf / weight / colour bit for bit (colour only where known), the
-    probability NaN exactly where `want`'s is, else within prob_tol.  Returns the largest probability difference."""
+    probability NaN exactly where `want`'s is, else within prob_tol.  Returns the largest probability difference.
+    tsdf_nan_payload=False: where `want`'s tsdf is NaN any NaN will do (two processors may pick different payloads);
+    everywhere else bit for bit as before."""
     g, w = by_position(got), by_position(want)
     assert len(g[0]) == len(w[0]), f"{what}: {len(g[0])} blocks, expected {len(w[0])}"
     assert np.array_equal(g[0], w[0]), f"{what}: block sets differ"
@@ -144,6 +146,8 @@ def assert_sets_match(got, want, colour_known=None, prob_tol=1e-4, what="", tsdf
         known = colour_known[np.argsort(keys(want[0]), kind="stable")]
     gt, wt = g[1].view(np.uint32), np.ascontiguousarray(w[1], dtype=F).view(np.uint32)
     bad = gt != wt
+    if not tsdf_nan_payload:
+        bad &= ~(np.isnan(g[1]) & np.isnan(w[1]))
     if tsdf_tol is not None:  # (inputs that are not the oracle's own: the parity bar instead of bit equality)
         bad = ~(np.abs(g[1] - w[1]) <= tsdf_tol)
     assert not bad.any(), (f"{what}: tsdf differs in {int(bad.sum())} voxels, first at block/voxel "
