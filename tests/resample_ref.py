@@ -5,7 +5,7 @@ RGBW_DTYPE, prob [n, 512] float32).  A pose is (qx, qy, qz, qw, tx, ty, tz), dst
 
 quat_rotate / se3_apply / se3_inverse are restated operation by operation in float32 (device_math.h), the trilinear
 formula is the one of tests/sample_ref.py.  The candidate search is NOT the engine's: `blocks_with_contribution` is a
-brute force over a padded box per source block (forward transform with the normalised quaternion in float64, two
+brute force over a padded box per source block (the float64 inverse of the map G itself defines, `forward_map`, two
 voxels of padding), every voxel of every block in it evaluated."""
 import numpy as np
 
@@ -176,21 +176,35 @@ def records(block_set):
 
 
 # ---- brute force: which destination blocks hold a contributing voxel -----------------------------------------
+def forward_map(pose, vs):
+    """the map the contract defines, turned round: a destination voxel d samples the source at g = A d + c with A the
+    linear part of quat_rotate(G.q, .) and c = G.t, so a source point g lands on d = A^-1 (g - c).  Taken from G itself
+    (float32, as the kernel gets it) in float64 -- NOT from the normalised pose: A = I + (R^T - I) / |q|^2 is no
+    rotation when |q|^2 != 1, and 1e-3 of scale is 32 voxels at the end of the grid.  Returns (A^-1 [3, 3], c [3]),
+    or None when c is not finite (no voxel is in range then)."""
+    q, c = transform(pose, vs)
+    x, y, z, w = (float(v) for v in q)
+    c = np.array([float(v) for v in c], dtype=np.float64)
+    if not (np.all(np.isfinite(c)) and np.all(np.isfinite([x, y, z, w]))):
+        return None
+    K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])  # qv x .
+    A = np.eye(3) + 2.0 * w * K + 2.0 * (K @ K)              # v + w * 2 (qv x v) + qv x 2 (qv x v)
+    return np.linalg.inv(A), c
+
+
 def padded_blocks(pose, vs, src_pos, pad=2.0):
     """every destination block inside [-4096, 4095] that holds an integer voxel of the box around a source block's
-    reach [8b - 1, 8b + 8], taken through the forward transform (normalised quaternion, float64) and padded by `pad`
-    voxels; distinct, sorted by (z, y, x)"""
-    p = np.array([F(v) for v in pose], dtype=np.float64)
-    x, y, z, w = p[:4] / np.linalg.norm(p[:4])
-    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-    t = p[4:] / float(F(vs))
+    reach [8b - 1, 8b + 8], taken through `forward_map` (float64) and padded by `pad` voxels -- the padding covers the
+    float32 evaluation of g alone (under 0.2 voxel at the end of the grid); distinct, sorted by (z, y, x)"""
+    fm = forward_map(pose, vs)
+    if fm is None:
+        return np.zeros((0, 3), dtype=np.int16)
+    Ai, c = fm
     found = set()
     corner = np.array([[(k >> a) & 1 for a in range(3)] for k in range(8)], dtype=np.float64)
     for b in np.asarray(src_pos, dtype=np.int64).reshape(-1, 3):
         g = 8.0 * b[None, :] - 1.0 + 9.0 * corner
-        d = g @ R.T + t
+        d = (g - c) @ Ai.T
         lo = np.maximum(np.ceil(d.min(axis=0) - pad), -32768).astype(np.int64) >> 3
         hi = np.minimum(np.floor(d.max(axis=0) + pad), 32767).astype(np.int64) >> 3
         if np.any(lo > hi):
