@@ -203,6 +203,44 @@ __device__ inline void st_agent_request(Request* p, const Request& r) {
   __hip_atomic_store(q + 1, w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Write-through stores for BULK streams nothing in the same launch reads back (the voxel update's three pool
+// streams, the candidate pass's texels).  A plain (or `nt`) store leaves its line dirty in the XCD's L2, and what
+// is still dirty when the launch ends is written back at the launch boundary, where nothing overlaps it; an `sc1`
+// store leaves L2 at once, while the launch still has other work.  Per lane: 4 and 8 bytes as relaxed agent-scope
+// atomic stores (global_store_dword / dwordx2 ... sc1), 16 bytes as a raw buffer store with the sc1 policy bit
+// (there is no 16-byte atomic store) -- all three are memory operations the compiler counts and schedules itself.
+// Which streams use them is a compile-time sweep default (like RATSDF_INTEG_NT; no environment variable):
+//   bit 1  voxel stores of the update write-through
+//   bit 2  texel stores of the candidate pass write-through
+//   bit 4  a wave of the update that stores, stores all 64 lanes' pairs (whole 128-byte lines; existing blocks:
+//          lanes without an update write back what they loaded, the same bytes)
+// Default 1 (same-box A/B, profiles/wt_stores_ab.txt): the voxel stores gain, the texel stores lose (an sc1 store
+// drops the line from L2, and the next frame's gathers then fetch it from memory), whole lines change nothing.
+#ifndef RATSDF_WT_STORES
+#define RATSDF_WT_STORES 1
+#endif
+constexpr bool kWtVoxels = (RATSDF_WT_STORES & 1) != 0;
+constexpr bool kWtTexels = (RATSDF_WT_STORES & 2) != 0;
+constexpr bool kWholeLineVoxels = (RATSDF_WT_STORES & 4) != 0;
+
+__device__ inline void st_wt(uint32_t* p, uint32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void st_wt(uint32_t* p, uint32_t v0, uint32_t v1) {  // p: 8-byte aligned
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v0 | ((unsigned long long)v1 << 32),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// 16 bytes at `base + byte_off`.  `base` and `bytes` (the array's size: the hardware drops a store beyond it) must be
+// the same in every lane of the wave -- the descriptor lives in scalar registers -- and byte_off a multiple of 16.
+__device__ inline void st_wt16(void* base, uint32_t bytes, uint32_t byte_off, const uint4& v) {
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+  constexpr int kRsrcFlags = 0x00020000;  // dword 3 of a gfx9 raw-buffer descriptor: DATA_FORMAT = 32
+  constexpr int kAuxSc1 = 16;             // cache-policy operand of the buffer builtins: the sc1 bit
+  __builtin_amdgcn_raw_buffer_store_b128(v4u{v.x, v.y, v.z, v.w},
+                                         __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, kRsrcFlags),
+                                         (int)byte_off, 0, kAuxSc1);
+}
+
 // alloc_request_absent for a whole wave (every lane calls it; `want` selects the lanes that have an
 // absent, visible block).
 __device__ inline void alloc_request_absent_wave(bool want, const Table& t, int x, int y, int z,

@@ -161,8 +161,15 @@ __device__ inline void cand_pixel_work(const CandJob& J, CandLds& L, uint32_t wg
     // update can use (finite, at most max_depth; a texel's w_new is read only when its voxel updates)
     const Recip rmd = make_recip(P.md);
     const float wn = (1 - (recip_safe(P.md) ? div_shared(d, rmd) : d / P.md)) * 4;
-    J.texA[pix] = make_float4(d, r, ln, wn);
-    J.texB[pix] = c;
+    // (read by the NEXT frame's update, never in this launch: kWtTexels, kernels_alloc.h)
+    if (kWtTexels) {
+      st_wt16(J.texA, (uint32_t)(P.W * P.H) * 16u, (uint32_t)pix * 16u,
+              make_uint4(__float_as_uint(d), __float_as_uint(r), __float_as_uint(ln), __float_as_uint(wn)));
+      st_wt(J.texB + pix, c);
+    } else {
+      J.texA[pix] = make_float4(d, r, ln, wn);
+      J.texB[pix] = c;
+    }
   }
   bool valid = inb && !(d == 0 || d > P.md);                            // :141
   if (RATSDF_DBG(P, 1)) return;  // uniform

@@ -56,6 +56,10 @@ struct VecIO<8> {
     reinterpret_cast<uint4*>(p)[0] = make_uint4(v[0], v[1], v[2], v[3]);
     reinterpret_cast<uint4*>(p)[1] = make_uint4(v[4], v[5], v[6], v[7]);
   }
+  static __device__ inline void store_wt(uint32_t* p, const uint32_t (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) st_wt(p + j, v[j], v[j + 1]);
+  }
 };
 template <>
 struct VecIO<4> {
@@ -65,6 +69,10 @@ struct VecIO<4> {
   }
   static __device__ inline void store(uint32_t* p, const uint32_t (&v)[4]) {
     reinterpret_cast<uint4*>(p)[0] = make_uint4(v[0], v[1], v[2], v[3]);
+  }
+  static __device__ inline void store_wt(uint32_t* p, const uint32_t (&v)[4]) {
+    st_wt(p, v[0], v[1]);
+    st_wt(p + 2, v[2], v[3]);
   }
 };
 template <>
@@ -76,13 +84,23 @@ struct VecIO<2> {
   static __device__ inline void store(uint32_t* p, const uint32_t (&v)[2]) {
     reinterpret_cast<uint2*>(p)[0] = make_uint2(v[0], v[1]);
   }
+  static __device__ inline void store_wt(uint32_t* p, const uint32_t (&v)[2]) { st_wt(p, v[0], v[1]); }
 };
 
 template <>
 struct VecIO<1> {
   static __device__ inline void load(const uint32_t* p, uint32_t (&v)[1]) { v[0] = p[0]; }
   static __device__ inline void store(uint32_t* p, const uint32_t (&v)[1]) { p[0] = v[0]; }
+  static __device__ inline void store_wt(uint32_t* p, const uint32_t (&v)[1]) { st_wt(p, v[0]); }
 };
+// A lane's voxels to one of the three pools, in the flavour RATSDF_WT_STORES selects (kernels_alloc.h).  The
+// write-through form goes out in 8-byte pieces at every VPL: the pools are addressed by 64-bit pointers that differ
+// from lane to lane, and the 16-byte form needs a base the whole wave shares.
+template <int VPL>
+__device__ inline void voxel_store(uint32_t* p, const uint32_t (&v)[VPL]) {
+  if (kWtVoxels) VecIO<VPL>::store_wt(p, v);
+  else VecIO<VPL>::store(p, v);
+}
 
 // ---------------------------------------------------------------------------------------------
 // The frame's serial role INSIDE k_integrate (256 threads, workgroup 0 of the launch).
@@ -95,7 +113,8 @@ struct VecIO<1> {
 // the update, publishes F->serial_done, and only those two consumers wait for it (bounded, like
 // carve_resolve_gate).
 // Hand-off WITHOUT cache maintenance in the ordinary frame: a release fence here would write back the
-// whole L2 of this XCD (which the update workgroups next door keep filling with dirty voxel lines), an
+// whole L2 of this XCD (dirty texel lines of the hosted candidate pass, and whatever else was stored plainly --
+// the update's own voxel stores are write-through, voxel_store, and leave no dirty line behind), an
 // acquire in every committing workgroup would drop theirs.  Instead the few words the commit needs
 // (winner flags, winners' ranks, alloc_base / n_win / n_winlist) are written with agent-scope stores
 // (write-through), drained (vmcnt) before the flag goes out the same way, and read with agent-scope
@@ -829,10 +848,15 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
   }
   }
   WSTAMP(3);
-  if ((nupd || fresh) && !RATSDF_DBG(P, 5) && !RATSDF_DBG(P, 7)) {
-    VecIO<VPL>::store(reinterpret_cast<uint32_t*>(pool.tsdf + v), tv);
-    if (segm_live || fresh) VecIO<VPL>::store(reinterpret_cast<uint32_t*>(pool.segm + v), sv);
-    VecIO<VPL>::store(pool.rgbw + v, cv);
+  // Nothing in this launch reads a voxel back (a block's arrays belong to one workgroup, in one pass of it), so
+  // the stores may leave L2 at once: voxel_store.  kWholeLineVoxels: when any lane of the wave updated, all 64 store
+  // -- whole 128-byte lines; a lane without an update holds what it loaded (the probability only where it WAS loaded).
+  bool st = nupd || fresh;
+  if (kWholeLineVoxels) st = fresh || __builtin_amdgcn_ballot_w64(nupd != 0) != 0ull;
+  if (st && !RATSDF_DBG(P, 5) && !RATSDF_DBG(P, 7)) {
+    voxel_store<VPL>(reinterpret_cast<uint32_t*>(pool.tsdf + v), tv);
+    if (segm_live || fresh) voxel_store<VPL>(reinterpret_cast<uint32_t*>(pool.segm + v), sv);
+    voxel_store<VPL>(pool.rgbw + v, cv);
   }
   // space_carving_kernel, :253-276: "min |tsdf| over the block >= 0.9" with fminf's NaN rule (a NaN
   // never wins) is "no voxel with |tsdf| < 0.9, and at least one that is a number": two per-lane
