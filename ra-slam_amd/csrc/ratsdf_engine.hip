@@ -25,6 +25,7 @@
 #include "kernels_surface.h"
 #include "kernels_fuse.h"
 #include "kernels_resample.h"
+#include "kernels_coarsen.h"
 #include "hip_mem.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
@@ -1959,3 +1960,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "mapfile.inc"  // ratsdf_save_map / ratsdf_load_map / ratsdf_map_file_info (include/ratsdf_map.h)
 #include "fuse.inc"     // ratsdf_fuse_map / ratsdf_fuse_blocks[_device] / ratsdf_fuse_map_file (include/ratsdf_fuse.h)
 #include "resample.inc" // ratsdf_resample_blocks_device / ratsdf_fuse_map_transformed (include/ratsdf_resample.h)
+#include "coarsen.inc"  // ratsdf_coarsen_blocks_device / ratsdf_fuse_map_coarsened (include/ratsdf_coarsen.h)

@@ -118,6 +118,65 @@ static std::vector<int16_t> resample_candidates(const Se3& G, const std::vector<
   return out;
 }
 
+// The source of a record-producing fusion: settled, sound, its live entries on the host (control data, read as
+// ratsdf_dump_directory reads them; no voxel crosses).  The source's stream is idle when this returns.
+static int fuse_source_blocks(ratsdf_engine* src, std::vector<ratsdf_block>* blocks) {
+  STCHK(src->settle());
+  STCHK(src->sticky());
+  STCHK(src->select(kSelValid, GridBounds{}, &src->ctl->n_sel));
+  uint32_t n_sel = 0;
+  STCHK(src->read_small(&n_sel, &src->ctl->n_sel, 4));
+  if (n_sel > src->vis_cap) return RATSDF_ERR_CAPACITY;
+  blocks->resize(n_sel);
+  if (n_sel == 0) return RATSDF_OK;
+  std::vector<int32_t> entry(n_sel);
+  return dump_selected_entries(src, n_sel, blocks->data(), entry.data());
+}
+
+// Candidate blocks of the destination lattice (n x 3 int16) turned into records by `launch(stream, m, d_pos, d_rec,
+// d_contrib)` in chunks of kMapChunk and fused: the empty ones dropped (k_resample_mark), the others through fuse_chunk.
+// Staging: the records of one chunk and their counts, made on the destination's stream (the source is settled and
+// idle), so the record path follows in stream order.
+template <class Launch>
+static int fuse_candidate_records(ratsdf_engine* dst, const std::vector<int16_t>& cand, Launch launch,
+                                  ratsdf_fuse_stats* stats) {
+  ratsdf_fuse_stats acc;
+  memset(&acc, 0, sizeof(acc));
+  const size_t n_cand = cand.size() / 3;
+  if (n_cand == 0) {  // nothing to launch
+    STCHK(dst->settle());
+    return dst->sticky();
+  }
+  FuseScratch s;
+  int32_t free_before = 0;
+  STCHK(fuse_begin(dst, &s, &free_before));
+  DevMem stage, counts;
+  StreamDrain drain{dst->stream};
+  STCHK(stage.alloc((size_t)kMapChunk * kMapRecordBytes));
+  STCHK(counts.alloc((size_t)kMapChunk * 4));
+  uint32_t* rec = stage.as<uint32_t>();
+  int st = RATSDF_OK;
+  for (size_t first = 0; first < n_cand && st == RATSDF_OK; first += kMapChunk) {
+    const int32_t m = (int32_t)std::min<size_t>(kMapChunk, n_cand - first);
+    if (hipMemcpyAsync(s.pos, cand.data() + first * 3, (size_t)m * 6, hipMemcpyHostToDevice, dst->stream) != hipSuccess) {
+      st = RATSDF_ERR_DEVICE;
+      break;
+    }
+    st = fuse_clear(dst, s);
+    if (st != RATSDF_OK) break;
+    st = launch(dst->stream, m, s.pos, rec, counts.as<int32_t>());
+    if (st != RATSDF_OK) break;
+    hipLaunchKernelGGL(k_resample_mark, dim3(((unsigned)m + 255u) / 256u), dim3(256), 0, dst->stream,
+                       counts.as<int32_t>(), (uint32_t)m, s.done, s.cnt);
+    uint32_t listed = 0;  // (control data: 4 bytes per chunk; a chunk of empty candidates needs no allocation pass)
+    st = dst->read_small(&listed, &s.cnt->listed, 4);
+    if (st != RATSDF_OK || listed == 0) continue;
+    acc.blocks_seen += listed;
+    st = fuse_chunk(dst, s, m, s.pos, nullptr, rec, rec + 512, rec + 1024, 1536u, &acc);
+  }
+  return fuse_end(dst, st, free_before, &acc, stats);
+}
+
 }  // namespace
 
 extern "C" {
@@ -137,59 +196,17 @@ int ratsdf_fuse_map_transformed(ratsdf_engine* dst, ratsdf_engine* src, const ra
                                 ratsdf_fuse_stats* stats) {
   ENTRY(dst, src && dst != src && dst->device == src->device && memcmp(&dst->vs, &src->vs, 4) == 0 &&
                  memcmp(&dst->trunc, &src->trunc, 4) == 0 && resample_pose_ok(dst_T_src));
-  ratsdf_fuse_stats acc;
-  memset(&acc, 0, sizeof(acc));
-  if (stats) *stats = acc;
-  // the source: settled, sound, the positions of its live entries on the host (as ratsdf_dump_directory)
-  STCHK(src->settle());
-  STCHK(src->sticky());
-  STCHK(src->select(kSelValid, GridBounds{}, &src->ctl->n_sel));
-  uint32_t n_sel = 0;
-  STCHK(src->read_small(&n_sel, &src->ctl->n_sel, 4));
-  if (n_sel > src->vis_cap) return RATSDF_ERR_CAPACITY;
-  std::vector<int16_t> cand;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  std::vector<ratsdf_block> blocks;
+  STCHK(fuse_source_blocks(src, &blocks));
   const Se3 G = resample_transform(dst_T_src, src->vs);
-  if (n_sel != 0) {
-    std::vector<ratsdf_block> blocks(n_sel);
-    std::vector<int32_t> entry(n_sel);
-    STCHK(dump_selected_entries(src, n_sel, blocks.data(), entry.data()));  // (the source's stream is idle from here on)
-    cand = resample_candidates(G, blocks, src->tab.num_block);
-  }
-  const size_t n_cand = cand.size() / 3;
-  if (n_cand == 0) {  // an empty source, or one wholly outside the destination's grid: nothing to launch
-    STCHK(dst->settle());
-    return dst->sticky();
-  }
-  FuseScratch s;
-  int32_t free_before = 0;
-  STCHK(fuse_begin(dst, &s, &free_before));
-  // staging: the records of one chunk of candidates and their counts; resampled on the destination's stream (the
-  // source is settled and idle), so the record path follows in stream order
-  DevMem stage, counts;
-  StreamDrain drain{dst->stream};
-  STCHK(stage.alloc((size_t)kMapChunk * kMapRecordBytes));
-  STCHK(counts.alloc((size_t)kMapChunk * 4));
-  uint32_t* rec = stage.as<uint32_t>();
-  int st = RATSDF_OK;
-  for (size_t first = 0; first < n_cand && st == RATSDF_OK; first += kMapChunk) {
-    const int32_t m = (int32_t)std::min<size_t>(kMapChunk, n_cand - first);
-    if (hipMemcpyAsync(s.pos, cand.data() + first * 3, (size_t)m * 6, hipMemcpyHostToDevice, dst->stream) != hipSuccess) {
-      st = RATSDF_ERR_DEVICE;
-      break;
-    }
-    st = fuse_clear(dst, s);
-    if (st != RATSDF_OK) break;
-    st = resample_launch(src, dst->stream, G, m, s.pos, rec, counts.as<int32_t>());
-    if (st != RATSDF_OK) break;
-    hipLaunchKernelGGL(k_resample_mark, dim3(((unsigned)m + 255u) / 256u), dim3(256), 0, dst->stream,
-                       counts.as<int32_t>(), (uint32_t)m, s.done, s.cnt);
-    uint32_t listed = 0;  // (control data: 4 bytes per chunk; a chunk of empty candidates needs no allocation pass)
-    st = dst->read_small(&listed, &s.cnt->listed, 4);
-    if (st != RATSDF_OK || listed == 0) continue;
-    acc.blocks_seen += listed;
-    st = fuse_chunk(dst, s, m, s.pos, nullptr, rec, rec + 512, rec + 1024, 1536u, &acc);
-  }
-  return fuse_end(dst, st, free_before, &acc, stats);
+  // (an empty source, or one wholly outside the destination's grid, has no candidates: nothing is launched)
+  return fuse_candidate_records(
+      dst, resample_candidates(G, blocks, src->tab.num_block),
+      [&](hipStream_t stream, int32_t m, const int16_t* d_pos, uint32_t* d_rec, int32_t* d_contrib) {
+        return resample_launch(src, stream, G, m, d_pos, d_rec, d_contrib);
+      },
+      stats);
 }
 
 }  // extern "C"

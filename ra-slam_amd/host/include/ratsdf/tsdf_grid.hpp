@@ -57,6 +57,8 @@ struct Api {
   int (*fuse_map_file)(ratsdf_engine*, const char*, ratsdf_fuse_stats*) = nullptr;
   // include/ratsdf_resample.h: likewise optional
   int (*fuse_map_transformed)(ratsdf_engine*, ratsdf_engine*, const ratsdf_pose*, ratsdf_fuse_stats*) = nullptr;
+  // include/ratsdf_coarsen.h: likewise optional
+  int (*fuse_map_coarsened)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -131,6 +133,9 @@ class TSDFGrid {
   // transformed map fusion (include/ratsdf_resample.h): another grid's map resampled onto this grid's lattice under
   // dst_T_src (p_dst = R(q) p_src + t, metres: a map-to-map pose, not a camera pose) and fused.  Return the status.
   int FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats = nullptr);
+  // map coarsening (include/ratsdf_coarsen.h): another grid's map of HALF this grid's voxel size (same device and
+  // truncation; only read) coarsened by two and fused into this map.  Return the status.
+  int FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats = nullptr);
   int last_status() const { return status_; }
   ratsdf_engine* handle() { return engine_; }
   const Api& api() const { return *api_; }

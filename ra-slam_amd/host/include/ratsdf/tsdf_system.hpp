@@ -155,6 +155,10 @@ class TSDFSystem {
                  ratsdf_fuse_stats* stats = nullptr);
   int FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats = nullptr);
   int FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats = nullptr);
+  // map coarsening (include/ratsdf_coarsen.h), both directions, Flush() first and under the engine's mutex likewise:
+  // `src` (half this map's voxel size) coarsened into this map; this map coarsened into `dst` (twice its voxel size)
+  int FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats = nullptr);
+  int CoarsenInto(TSDFGrid& dst, ratsdf_fuse_stats* stats = nullptr);
   // TSDFGrid::ESDF under the engine's mutex, like Sample
   int ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
            uint8_t* state = nullptr);

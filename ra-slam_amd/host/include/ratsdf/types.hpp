@@ -17,6 +17,7 @@
 #include "../../../../include/ratsdf_sample.h"
 #include "../../../../include/ratsdf_fuse.h"
 #include "../../../../include/ratsdf_resample.h"
+#include "../../../../include/ratsdf_coarsen.h"
 #include "../../../../include/ratsdf_esdf.h"
 #include "../../../../include/ratsdf_surface.h"
 

@@ -20,6 +20,9 @@
 //          [--load-map FILE (a map checkpoint to continue, before the first frame; its voxel size must be --voxel)]
 //          [--first-frame K (skip the first K frames of the dataset)] [--save-map FILE (after the last frame)]
 //          [--fuse-map FILE (a checkpoint fused into the map after the last frame, before --save-map / the downloads)]
+//          [--save-coarse-map FILE [--coarse-levels K (default 1, 1 .. 8)] (after the last frame and --fuse-map: the
+//          checkpoint of the map coarsened K times by two, include/ratsdf_coarsen.h -- voxel size 2^K * --voxel, same
+//          truncation; the levels are chained through temporary grids)]
 //          [--surface-points FILE (after the last frame: the oriented surface points of the map's bounding box,
 //          32-byte records of include/ratsdf_surface.h, min_weight 1; a box beyond 512 voxels along an axis is
 //          covered by block-aligned boxes of at most 512, z then y then x, each in the header's order)]
@@ -79,6 +82,26 @@ int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
   fprintf(stderr, "[offline_eval] %zu surface points to %s\n", all.size(), path.c_str());
   return RATSDF_OK;
 }
+
+// the map coarsened `levels` times by two (include/ratsdf_coarsen.h) as a checkpoint: a chain of grids of twice the
+// voxel size each, a level destroyed as soon as the next one exists
+int write_coarse_map(TSDFSystem& tsdf, const Api& api, float vs, float trunc, int device, int levels,
+                     const std::string& path) {
+  std::unique_ptr<TSDFGrid> cur;
+  for (int l = 0; l < levels; ++l) {
+    vs = 2.0f * vs;
+    auto next = std::make_unique<TSDFGrid>(vs, trunc, device, &api);
+    if (next->last_status() != RATSDF_OK) return next->last_status();
+    ratsdf_fuse_stats fs;
+    memset(&fs, 0, sizeof(fs));
+    const int st = cur ? next->FuseMapCoarsened(*cur, &fs) : tsdf.CoarsenInto(*next, &fs);
+    if (st != RATSDF_OK) return st;
+    fprintf(stderr, "[offline_eval] level %d: voxel size %g, %lld blocks, %lld voxels\n", l + 1, vs,
+            (long long)fs.blocks_allocated, (long long)fs.voxels_copied);
+    cur = std::move(next);
+  }
+  return cur->SaveMap(path);
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -90,7 +113,8 @@ int main(int argc, char** argv) {
   const char* lib = nullptr;
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
-  std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points;
+  std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points, save_coarse_map;
+  int coarse_levels = 1;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -116,11 +140,17 @@ int main(int argc, char** argv) {
     else if (a == "--save-map") save_map = next();
     else if (a == "--fuse-map") fuse_map = next();
     else if (a == "--surface-points") surface_points = next();
+    else if (a == "--save-coarse-map") save_coarse_map = next();
+    else if (a == "--coarse-levels") coarse_levels = atoi(next());
     else if (a == "--first-frame") first_frame = atoi(next());
     else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
       return 2;
     }
+  }
+  if (coarse_levels < 1 || coarse_levels > 8) {
+    fprintf(stderr, "--coarse-levels must lie in 1 .. 8\n");
+    return 2;
   }
   const bool is_sens = data_path.size() > 5 && data_path.substr(data_path.size() - 5) == ".sens";
   try {
@@ -219,6 +249,15 @@ int main(int argc, char** argv) {
                 (long long)fs.voxels_averaged);
       }
       if (!save_map.empty() && tsdf->SaveMap(save_map) != RATSDF_OK) return 1;
+      if (!save_coarse_map.empty()) {
+        const int st = write_coarse_map(*tsdf, Api::Load(lib), voxel_size, voxel_size * 6, device, coarse_levels,
+                                        save_coarse_map);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --save-coarse-map %s: %s\n", save_coarse_map.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
       if (!download_all.empty()) tsdf->DownloadAll(download_all);
       if (!download_mesh.empty())  // offline_eval.cc:95-98
         tsdf->DownloadAllMesh(download_mesh + "_vertices.bin", download_mesh + "_indices.bin",

@@ -82,6 +82,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.fuse_blocks = reinterpret_cast<decltype(api.fuse_blocks)>(opt_sym("fuse_blocks"));
   api.fuse_map_file = reinterpret_cast<decltype(api.fuse_map_file)>(opt_sym("fuse_map_file"));
   api.fuse_map_transformed = reinterpret_cast<decltype(api.fuse_map_transformed)>(opt_sym("fuse_map_transformed"));
+  api.fuse_map_coarsened = reinterpret_cast<decltype(api.fuse_map_coarsened)>(opt_sym("fuse_map_coarsened"));
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
   return loaded.emplace(key, api).first->second;
@@ -261,6 +262,13 @@ int TSDFGrid::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ra
   note(api_->fuse_map_transformed ? api_->fuse_map_transformed(engine_, src.engine_, &dst_T_src, stats)
                                   : RATSDF_ERR_NOT_IMPLEMENTED,
        "FuseMapTransformed");
+  return status_;
+}
+
+int TSDFGrid::FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats) {
+  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  note(api_->fuse_map_coarsened ? api_->fuse_map_coarsened(engine_, src.engine_, stats) : RATSDF_ERR_NOT_IMPLEMENTED,
+       "FuseMapCoarsened");
   return status_;
 }
 
@@ -570,6 +578,18 @@ int TSDFSystem::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, 
   Flush();
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.FuseMapTransformed(src, dst_T_src, stats);
+}
+
+int TSDFSystem::FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.FuseMapCoarsened(src, stats);
+}
+
+int TSDFSystem::CoarsenInto(TSDFGrid& dst, ratsdf_fuse_stats* stats) {
+  Flush();
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return dst.FuseMapCoarsened(tsdf_, stats);
 }
 
 int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {

@@ -100,6 +100,8 @@ FUSE_STATS = np.dtype([("blocks_seen", "<i8"), ("blocks_allocated", "<i8"), ("bl
 assert FUSE_STATS.itemsize == 40
 # include/ratsdf_resample.h (transformed map fusion): handled like FUSE_SYMBOLS
 RESAMPLE_SYMBOLS = ["resample_blocks_device", "fuse_map_transformed"]
+# include/ratsdf_coarsen.h (map coarsening): handled like RESAMPLE_SYMBOLS
+COARSEN_SYMBOLS = ["coarsen_blocks_device", "fuse_map_coarsened"]
 ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
 # include/ratsdf_surface.h (oriented surface points of a box): handled like ESDF_SYMBOLS
 SURFACE_SYMBOLS = ["surface_points", "surface_points_device"]
@@ -272,6 +274,15 @@ class Library:
                 f.argtypes = {"resample_blocks_device": [vp, C.POINTER(Pose), C.c_int32, vp, vp, vp],
                               "fuse_map_transformed": [vp, vp, C.POINTER(Pose), vp]}[s]
             self.fn[s] = f
+        for s in COARSEN_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = {"coarsen_blocks_device": [vp, C.c_int32, vp, vp, vp],
+                              "fuse_map_coarsened": [vp, vp, vp]}[s]
+            self.fn[s] = f
 
     def backend(self):
         return self.fn["backend"]().decode()
@@ -346,6 +357,7 @@ class Engine:
         self.lib = lib
         self.voxel_size = float(voxel_size)
         self.truncation = float(truncation)
+        self.device = int(device)
         cfg = Config()
         cfg.voxel_size = voxel_size
         cfg.truncation = truncation
@@ -773,6 +785,49 @@ class Engine:
         p = _as_pose(dst_T_src)
         _check(self.lib.fn["resample_blocks_device"](self._h, C.byref(p), int(n), d_block_pos or None,
                                                      d_voxels or None, d_contrib or None), "resample_blocks_device")
+
+    # -- map coarsening (include/ratsdf_coarsen.h) -----------------------------------------
+    def fuse_map_coarsened(self, src):
+        """coarsens the map of ``src`` (an Engine on the same device, of HALF this map's voxel size and the same
+        truncation) by two and fuses it into this map; ``src`` is only read.  Returns the statistics (raises like the
+        other fusion calls)."""
+        return self._fuse("fuse_map_coarsened", src._h)
+
+    def coarsen_blocks_device(self, n, d_block_pos, d_voxels, d_contrib=0):
+        """blocks of the lattice of TWICE this map's voxel size (d_block_pos: n x 3 int16) filled from this map:
+        d_voxels gets n records in export_blocks_device()'s layout, d_contrib (or 0) one int32 per block, the number of
+        contributing voxels.  Device pointers; asynchronous on this engine's stream."""
+        _check(self.lib.fn["coarsen_blocks_device"](self._h, int(n), d_block_pos or None, d_voxels or None,
+                                                    d_contrib or None), "coarsen_blocks_device")
+
+    def coarsened(self, levels=1, **create_kw):
+        """a new engine of the same library, device and truncation holding this map at float32(voxel_size) *
+        2**levels: `levels` coarsenings by two in a chain (1 .. 8), each temporary level destroyed as soon as the next
+        one exists.  ``create_kw`` (block_bits, bucket_bits, ...) goes to every engine of the chain.  The caller closes
+        the result."""
+        levels = int(levels)
+        if not 1 <= levels <= 8:
+            raise ValueError("levels must lie in 1 .. 8")
+        create_kw.setdefault("device", self.device)
+        cur = self
+        try:
+            for _ in range(levels):
+                vs = float(np.float32(2.0) * np.float32(cur.voxel_size))
+                nxt = object.__new__(type(self))  # (a TSDFGrid stays a TSDFGrid: it adds no state of its own)
+                Engine.__init__(nxt, self.lib, vs, self.truncation, **create_kw)
+                try:
+                    nxt.fuse_map_coarsened(cur)
+                except Exception:
+                    nxt.close()
+                    raise
+                if cur is not self:
+                    cur.close()
+                cur = nxt
+        except Exception:
+            if cur is not self:
+                cur.close()
+            raise
+        return cur
 
     # -- test hooks ------------------------------------------------------------------------
     @staticmethod
