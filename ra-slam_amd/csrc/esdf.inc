@@ -4,7 +4,6 @@
 extern "C" {
 
 constexpr size_t kEsdfMaxVoxels = (size_t)1 << 27;
-constexpr size_t kEsdfHostChunk = (size_t)32 << 20;  // bytes of the host entry point's page-locked pass-through
 
 // the workspace of a box of n voxels: state (n B) | x pass (4n B; the host entry point's field after the z pass) |
 // y pass (8n B) | stack of the transform to O (8n B) | stack of the transform to box \ O (8n B)
@@ -17,7 +16,7 @@ static size_t esdf_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 static size_t esdf_work_bytes(size_t n) { return esdf_round(n) + esdf_round(4 * n) + 3 * esdf_round(8 * n); }
 
 // argument checks of both entry points (RATSDF_ERR_BAD_ARGUMENT when false)
-static bool esdf_box(const int32_t* origin, const int32_t* dims, float occupied_below, uint32_t flags, EsdfBox* b,
+static bool esdf_box(const int32_t* origin, const int32_t* dims, float occupied_below, uint32_t flags, MapBox* b,
                      size_t* n) {
   if (!origin || !dims || std::isnan(occupied_below) || (flags & ~RATSDF_ESDF_UNKNOWN_OCCUPIED)) return false;
   size_t m = 1;
@@ -53,11 +52,10 @@ static int esdf_workspace(ratsdf_engine* e, size_t n, EsdfWork* w) {
   return RATSDF_OK;
 }
 
-static int esdf_launch(ratsdf_engine* e, const EsdfBox& b, size_t n, float occupied_below, uint32_t flags,
+static int esdf_launch(ratsdf_engine* e, const MapBox& b, size_t n, float occupied_below, uint32_t flags,
                        const EsdfWork& w, float* d_out, uint8_t* d_state) {
   uint8_t* st = d_state ? d_state : w.st;
-  const int nbz = ((b.oz + b.Z - 1) >> 3) - b.bz0 + 1;
-  hipLaunchKernelGGL(k_esdf_seed, dim3((unsigned)(b.nbx * b.nby * nbz)), dim3(256), 0, e->stream, e->tab, e->pool, b,
+  hipLaunchKernelGGL(k_esdf_seed, dim3((unsigned)box_cells(b)), dim3(256), 0, e->stream, e->tab, e->pool, b,
                      occupied_below, st);
   HIPCHK(hipGetLastError());
   const uint32_t omask = (1u << kEsdfOccupied) | ((flags & RATSDF_ESDF_UNKNOWN_OCCUPIED) ? 1u << kEsdfUnknown : 0u);
@@ -78,7 +76,7 @@ static int esdf_launch(ratsdf_engine* e, const EsdfBox& b, size_t n, float occup
 
 int ratsdf_esdf_device(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3], float occupied_below,
                        uint32_t flags, void* d_out, void* d_state) {
-  EsdfBox b;
+  MapBox b;
   size_t n = 0;
   ENTRY(e, d_out && !((uintptr_t)d_out & 15u) && esdf_box(origin, dims, occupied_below, flags, &b, &n));
   STCHK(e->settle());
@@ -90,26 +88,18 @@ int ratsdf_esdf_device(ratsdf_engine* e, const int32_t origin[3], const int32_t 
 
 int ratsdf_esdf(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3], float occupied_below,
                 uint32_t flags, float* out, uint8_t* state) {
-  EsdfBox b;
+  MapBox b;
   size_t n = 0;
   ENTRY(e, out && esdf_box(origin, dims, occupied_below, flags, &b, &n));
   STCHK(e->settle());
   STCHK(sticky_raised(e));
   EsdfWork w;
   STCHK(esdf_workspace(e, n, &w));
-  STCHK(e->h_esdf.grow(kEsdfHostChunk));
-  uint8_t* const h = e->h_esdf.as<uint8_t>();
+  STCHK(e->staging(0, kHostChunk));
   // the field lands in the x pass's buffer, dead once the y pass has run
   STCHK(esdf_launch(e, b, n, occupied_below, flags, w, (float*)w.gx, nullptr));
-  const struct { const uint8_t* src; uint8_t* dst; size_t bytes; } parts[2] = {
-      {(const uint8_t*)w.gx, (uint8_t*)out, n * sizeof(float)}, {w.st, state, state ? n : 0}};
-  for (const auto& p : parts)
-    for (size_t o = 0; o < p.bytes; o += kEsdfHostChunk) {
-      const size_t m = std::min(kEsdfHostChunk, p.bytes - o);
-      HIPCHK(hipMemcpyAsync(h, p.src + o, m, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      memcpy(p.dst + o, h, m);
-    }
+  STCHK(e->download(out, w.gx, n * sizeof(float)));
+  if (state) STCHK(e->download(state, w.st, n));
   return e->sticky();
 }
 

@@ -43,15 +43,8 @@ __global__ __launch_bounds__(512) void k_coarsen_blocks(Table tab, Pool pool, co
   const uint32_t v = threadIdx.x;  // x + 8y + 64z
   const int bx = pos[3 * b], by = pos[3 * b + 1], bz = pos[3 * b + 2];
   if (v < 27u) {
-    int32_t idx = -1;
     const int x = 2 * bx - 1 + (int)(v % 3u), y = 2 * by - 1 + (int)((v / 3u) % 3u), z = 2 * bz - 1 + (int)(v / 9u);
-    if (x >= -4096 && x <= 4095 && y >= -4096 && y <= 4095 && z >= -4096 && z <= 4095) {
-      EntryWords w;
-      const uint32_t e = find_block(tab, x, y, z, &w);
-      // (an entry left pending by a failed frame, kPlaceholderIdx, names no pool block: absent, never read)
-      if (e != kInf && w.idx >= 0 && w.idx < tab.num_block) idx = w.idx;
-    }
-    s_blk[v] = idx;
+    s_blk[v] = block_in_grid(x, y, z) ? lookup_block(tab, x, y, z) : -1;
   }
   __syncthreads();
 

@@ -16,7 +16,7 @@
 // every term of Sep and of the envelope comparison stays below 2^30 + 3 * 1023^2 < 2^31.
 // The map is only read: no directory entry, pool word, free-list slot or delta bit is written.
 #pragma once
-#include "kernels_sample.h"
+#include "map_read.h"
 
 namespace ratsdf {
 
@@ -24,25 +24,14 @@ constexpr int32_t kEsdfInf = 1 << 30;
 constexpr uint32_t kEsdfUnknown = 0u, kEsdfFree = 1u, kEsdfOccupied = 2u;  // RATSDF_ESDF_STATE_*
 constexpr int kEsdfColWG = 64;  // lanes (columns) per workgroup of k_esdf_col: small boxes have few columns
 
-struct EsdfBox {
-  int ox, oy, oz;     // voxel index of the minimum corner
-  int X, Y, Z;        // voxels per axis
-  int bx0, by0, bz0;  // the first map block the box meets
-  int nbx, nby;       // map blocks per axis it meets (x, y)
-};
-
 // state bytes of the box's voxels that lie in one map block (blockIdx.x: the block, x fastest)
-__global__ __launch_bounds__(256) void k_esdf_seed(Table tab, Pool pool, EsdfBox b, float occupied_below,
+__global__ __launch_bounds__(256) void k_esdf_seed(Table tab, Pool pool, MapBox b, float occupied_below,
                                                    uint8_t* __restrict__ st) {
   __shared__ int32_t s_blk;
   const uint32_t g = blockIdx.x;
   const int bx = b.bx0 + (int)(g % (uint32_t)b.nbx), by = b.by0 + (int)((g / (uint32_t)b.nbx) % (uint32_t)b.nby);
   const int bz = b.bz0 + (int)(g / ((uint32_t)b.nbx * (uint32_t)b.nby));
-  if (threadIdx.x == 0) {
-    const uint32_t e0 = block_hash(bx, by, bz, tab.bucket_mask) << 1;
-    const int32_t r = sample_resolve(tab, bx, by, bz, e0, load_entry(tab.entries, e0), load_entry(tab.entries, e0 + 1));
-    s_blk = r < tab.num_block ? r : -1;  // (a pending entry, kPlaceholderIdx, names no pool block: absent)
-  }
+  if (threadIdx.x == 0) s_blk = lookup_block(tab, bx, by, bz);  // (the box lies inside the grid: esdf_box)
   __syncthreads();
   const int32_t blk = s_blk;
 #pragma unroll

@@ -11,7 +11,7 @@
 // pass that fused it (or found that the shard filter refuses it); later passes skip the block.  What is still missing
 // is counted per pass.
 #pragma once
-#include "kernels_alloc.h"
+#include "map_read.h"
 
 namespace ratsdf {
 
@@ -122,14 +122,13 @@ __global__ __launch_bounds__(256) void k_fuse_blocks(Table tab, Pool pool, Frame
       ++n_skipped;
       continue;
     }
-    EntryWords w;
-    const uint32_t e = find_block(tab, x, y, z, &w);
-    if (e == kInf || w.idx < 0 || w.idx >= tab.num_block) {  // (kPlaceholderIdx: a pending entry names no pool block)
+    const int32_t idx = lookup_block(tab, x, y, z);
+    if (idx < 0) {
       ++n_missing;
       continue;
     }
     const size_t so = (size_t)(src_idx ? (uint32_t)src_idx[b] : b) * stride + lane * 8u;
-    const size_t d = ((size_t)w.idx << 9) + lane * 8u;
+    const size_t d = ((size_t)idx << 9) + lane * 8u;
     const uint4* ps[3] = {reinterpret_cast<const uint4*>(s_tsdf + so), reinterpret_cast<const uint4*>(s_rgbw + so),
                           reinterpret_cast<const uint4*>(s_prob + so)};
     uint4* pd[3] = {reinterpret_cast<uint4*>(pool.tsdf + d), reinterpret_cast<uint4*>(pool.rgbw + d),

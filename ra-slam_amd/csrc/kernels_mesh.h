@@ -63,12 +63,9 @@ __global__ __launch_bounds__(512) void k_marching_cubes(Table tab, Pool pool, co
   const VisItem base = blocks[bi];
   const int tid = threadIdx.x;
   const int tx = tid & 7, ty = (tid >> 3) & 7, tz = tid >> 6;
-  if (tid < 8) {  // GetBlock of the 2x2x2 neighbourhood, voxel_tsdf.cu:582-586
-    EntryWords w;
-    const uint32_t e = find_block(tab, (int16_t)(base.x + (tid & 1)), (int16_t)(base.y + ((tid >> 1) & 1)),
-                                  (int16_t)(base.z + (tid >> 2)), &w);
-    nb_idx[tid] = e == kInf ? -1 : w.idx;
-  }
+  if (tid < 8)  // GetBlock of the 2x2x2 neighbourhood, voxel_tsdf.cu:582-586
+    nb_idx[tid] = lookup_block(tab, (int16_t)(base.x + (tid & 1)), (int16_t)(base.y + ((tid >> 1) & 1)),
+                               (int16_t)(base.z + (tid >> 2)));
   __syncthreads();
 #pragma unroll
   for (int n = 0; n < 8; ++n) {  // n = x + 2y + 4z of the neighbour

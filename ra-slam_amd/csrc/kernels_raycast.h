@@ -13,7 +13,7 @@
 // but took 450 - 520 us; half of the waves are through after 90 us; the kernel lasts as long as its slowest waves,
 // and those hold a ray that runs its FULL length (534 samples: it leaves through a gap, or grazes a surface), every
 // sample of it a directory probe that finds nothing -- 64 % of such a lane's cycles were probes, one after the other
-// (find_block branches on what it loaded, so four probes in a row are four round trips of ~0.7 us), 32 % the judging
+// (a lookup branches on what it loaded, so four probes in a row are four round trips of ~0.7 us), 32 % the judging
 // code, 5 % the voxel loads.  Hence:
 //   * occupancy in LDS, two levels: k_occupancy_build hashes every live block into a 16 KiB Bloom filter (two bits per
 //     block) and its super-cell of 4^3 blocks into a 4 KiB bitmap before the rendering (a scan of Table::active), every
@@ -31,6 +31,7 @@
 // lookups that remain are LDS reads, and a group's extra samples only lengthen the slowest wave's instruction stream).
 #pragma once
 #include "kernels_integrate.h"
+#include "map_read.h"
 
 namespace ratsdf {
 
@@ -69,20 +70,14 @@ __device__ inline bool occ_maybe(const uint32_t* occ, int bx, int by, int bz) {
 }
 
 // pool voxel index of integer voxel (px,py,pz) or -1 (block absent).  `occ`: the occupancy bits (LDS) -- a clear bit
-// proves the block absent and saves the directory probe.
+// proves the block absent and saves the directory probe.  (px, py, pz are int16 values: the block lies inside the grid.)
 __device__ inline long voxel_index(const Table& tab, int px, int py, int pz, BlockCache& c, const uint32_t* occ) {
   const int bx = px >> 3, by = py >> 3, bz = pz >> 3;
   if (!(c.valid && c.bx == bx && c.by == by && c.bz == bz)) {
-    int32_t idx = -1;
-    if (occ_maybe(occ, bx, by, bz)) {
-      EntryWords w;
-      const uint32_t e = find_block(tab, bx, by, bz, &w);
-      idx = e == kInf ? -1 : w.idx;
-    }
     c.bx = bx;
     c.by = by;
     c.bz = bz;
-    c.idx = idx;
+    c.idx = occ_maybe(occ, bx, by, bz) ? lookup_block(tab, bx, by, bz) : -1;
     c.valid = true;
   }
   if (c.idx < 0) return -1;

@@ -18,7 +18,7 @@
 //     2 x 2 x 2);
 //   * every voxel's 8 tsdf loads, 8 rgbw loads and the probability load are issued before any is used.  They are not
 //     predicated: a corner that is not needed or whose block is absent reads voxel 0 of pool block 0, which exists, and
-//     drops the value (k_sample explains why a branch around the loads would serialise them);
+//     drops the value (kernels_sample.h explains why a branch around the loads would serialise them);
 //   * the record leaves as three plain vector stores, lane = voxel: whole lines per wave and plane.
 // The source map is only read.
 #pragma once
@@ -39,9 +39,7 @@ __global__ __launch_bounds__(512) void k_resample_blocks(Table tab, Pool pool, S
   // the contract of include/ratsdf_resample.h, evaluated as written (-ffp-contract=off)
   const V3 g = se3_apply(G, V3{(float)dx, (float)dy, (float)dz});
   const float lxf = floorf(g.x), lyf = floorf(g.y), lzf = floorf(g.z);
-  // every corner inside the int16 voxel range (a NaN fails every comparison; +-inf fails one): no wrap-around
-  const bool in_grid = lxf >= -32768.f && lxf <= 32766.f && lyf >= -32768.f && lyf <= 32766.f && lzf >= -32768.f &&
-                       lzf <= 32766.f;
+  const bool in_grid = cell_in_grid(lxf, lyf, lzf);
   const int lx = in_grid ? (int)lxf : 0, ly = in_grid ? (int)lyf : 0, lz = in_grid ? (int)lzf : 0;
   if (v < 3u) s_min[v] = INT_MAX;
   __syncthreads();
@@ -63,15 +61,9 @@ __global__ __launch_bounds__(512) void k_resample_blocks(Table tab, Pool pool, S
   const bool any = s_min[0] != INT_MAX;  // (uniform) a voxel of the block falls inside the grid
   const int base_x = any ? s_min[0] >> 3 : 0, base_y = any ? s_min[1] >> 3 : 0, base_z = any ? s_min[2] >> 3 : 0;
   if (v < 27u) {
-    int32_t idx = -1;
     const int x = base_x + (int)(v % 3u), y = base_y + (int)((v / 3u) % 3u), z = base_z + (int)(v / 9u);
-    if (any && x <= 4095 && y <= 4095 && z <= 4095) {  // (base >= -4096; a block past 4095 holds no voxel of the grid)
-      EntryWords w;
-      const uint32_t e = find_block(tab, x, y, z, &w);
-      // (an entry left pending by a failed frame, kPlaceholderIdx, names no pool block: absent, never read)
-      if (e != kInf && w.idx >= 0 && w.idx < tab.num_block) idx = w.idx;
-    }
-    s_blk[v] = idx;
+    // (base >= -4096; a block past 4095 holds no voxel of the grid)
+    s_blk[v] = any && x <= 4095 && y <= 4095 && z <= 4095 ? lookup_block(tab, x, y, z) : -1;
   }
   __syncthreads();
 
@@ -133,10 +125,7 @@ __global__ __launch_bounds__(512) void k_resample_blocks(Table tab, Pool pool, S
     }
     if (k == kn) cn = c[k];
   }
-  const float c00 = t[0] * uz + t[1] * fz, c01 = t[2] * uz + t[3] * fz;
-  const float c10 = t[4] * uz + t[5] * fz, c11 = t[6] * uz + t[7] * fz;
-  const float c0 = c00 * uy + c01 * fy, c1 = c10 * uy + c11 * fy;
-  const float tsdf = c0 * ux + c1 * fx;
+  const float tsdf = trilinear(t, fx, fy, fz, ux, uy, uz).value;
   uint32_t* rec = out + (size_t)b * 1536u + v;
   rec[0] = ok ? __float_as_uint(tsdf) : 0u;
   rec[512] = ok ? (cn & 0x00FFFFFFu) | (wmin << 24) : 0u;

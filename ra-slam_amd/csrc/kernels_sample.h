@@ -14,29 +14,11 @@
 //   * the record leaves as two 16-byte stores.
 // The map is only read: no directory entry, pool word, free-list slot or delta bit is written.
 #pragma once
-#include "kernels_alloc.h"
+#include "map_read.h"
 
 namespace ratsdf {
 
 constexpr uint32_t kSampleAllocated = 1u, kSampleObserved = 2u, kSampleNearest = 4u;  // RATSDF_SAMPLE_*
-
-// the pool index of block (x, y, z), -1 if absent: the chain walk of find_block from the home pair already loaded
-__device__ inline int32_t sample_resolve(const Table& t, int x, int y, int z, uint32_t e0, const EntryWords& a,
-                                         const EntryWords& b) {
-  const uint32_t k0 = key0(x, y), k1 = key1(z);
-  if (entry_matches(a, k0, k1)) return a.idx;
-  if (entry_matches(b, k0, k1)) return b.idx;
-  uint32_t last = e0 + 1;
-  int off = entry_offset(b);
-  uint32_t guard = 0;
-  while (off && guard++ < t.num_entry) {
-    last = (last + (uint32_t)off) & t.entry_mask;
-    const EntryWords w = load_entry(t.entries, last);
-    if (entry_matches(w, k0, k1)) return w.idx;
-    off = entry_offset(w);
-  }
-  return -1;
-}
 
 // out: 2 uint4 per point (the 32-byte ratsdf_sample).  xyz: 3 floats per point (metres).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_sample(Table tab, Pool pool, const float* __restrict__ xyz, int n, float vs,
@@ -48,11 +30,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
   const float lxf = floorf(gx), lyf = floorf(gy), lzf = floorf(gz);
   // defaults: tsdf / grad the quiet NaN 0x7FC00000 (outputs compare byte for byte), everything else 0
   uint4 r0 = make_uint4(0x7FC00000u, 0x7FC00000u, 0x7FC00000u, 0x7FC00000u), r1 = make_uint4(0u, 0u, 0u, 0u);
-  // every corner inside the int16 voxel range (a NaN fails every comparison; +-inf fails one): no wrap-around onto a
-  // real block
-  const bool in_grid = lxf >= -32768.f && lxf <= 32766.f && lyf >= -32768.f && lyf <= 32766.f && lzf >= -32768.f &&
-                       lzf <= 32766.f;
-  if (in_grid) {
+  if (cell_in_grid(lxf, lyf, lzf)) {
     const int lx = (int)lxf, ly = (int)lyf, lz = (int)lzf;
     const float fx = gx - lxf, fy = gy - lyf, fz = gz - lzf;
     const float ux = 1.f - fx, uy = 1.f - fy, uz = 1.f - fz;
@@ -79,9 +57,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
       const int mm = m & span;
-      const int32_t r = sample_resolve(tab, bx + (mm & 1), by + ((mm >> 1) & 1), bz + ((mm >> 2) & 1), e0[m], ha[m], hb[m]);
-      // (an entry left pending by a failed frame, kPlaceholderIdx, names no pool block: absent, never read)
-      blk[m] = r < tab.num_block ? r : -1;
+      blk[m] = resolve_block(tab, bx + (mm & 1), by + ((mm >> 1) & 1), bz + ((mm >> 2) & 1), e0[m], ha[m], hb[m]);
     }
     // every voxel load before any use (not predicated either: a corner whose block is absent reads voxel 0 of pool
     // block 0, which exists, and drops the value)
@@ -113,14 +89,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
       for (int k = 0; k < 8; ++k) wmin = min(wmin, c[k] >> 24);
       flags |= kSampleAllocated | (wmin >= 1u ? kSampleObserved : 0u);
       // the contract of include/ratsdf_sample.h, evaluated as written (-ffp-contract=off)
-      const float c00 = t[0] * uz + t[1] * fz, c01 = t[2] * uz + t[3] * fz;
-      const float c10 = t[4] * uz + t[5] * fz, c11 = t[6] * uz + t[7] * fz;
-      const float c0 = c00 * uy + c01 * fy, c1 = c10 * uy + c11 * fy;
-      const float tsdf = c0 * ux + c1 * fx;
-      const float dx = (c1 - c0) / vs;
-      const float dy = ((c01 - c00) * ux + (c11 - c10) * fx) / vs;
+      const Trilinear s = trilinear(t, fx, fy, fz, ux, uy, uz);
+      const float dx = (s.c1 - s.c0) / vs;
+      const float dy = ((s.c01 - s.c00) * ux + (s.c11 - s.c10) * fx) / vs;
       const float dz = (((t[1] - t[0]) * uy + (t[3] - t[2]) * fy) * ux + ((t[5] - t[4]) * uy + (t[7] - t[6]) * fy) * fx) / vs;
-      r0 = make_uint4(__float_as_uint(tsdf), __float_as_uint(dx), __float_as_uint(dy), __float_as_uint(dz));
+      r0 = make_uint4(__float_as_uint(s.value), __float_as_uint(dx), __float_as_uint(dy), __float_as_uint(dz));
     }
     r1 = make_uint4(__float_as_uint(prob), cn, wmin | (flags << 8), 0u);
   }

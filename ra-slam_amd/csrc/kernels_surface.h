@@ -22,8 +22,8 @@
 // (lds_barrier, kernels_carve.h).  The map is only read: no directory entry, pool word, free-list slot or delta bit
 // is written.
 #pragma once
-#include "kernels_esdf.h"
 #include "kernels_mesh.h"
+#include "map_read.h"
 
 namespace ratsdf {
 
@@ -32,7 +32,7 @@ constexpr int kSurfRow = 24, kSurfPlane = 11 * kSurfRow, kSurfVolume = 11 * kSur
 // cnt: points per cell (written by the count pass, read by the emit pass); pos / total: the scan's results; out: 2
 // uint4 per point (the 32-byte ratsdf_surface_point)
 template <bool kEmit>
-__global__ __launch_bounds__(512) void k_surface(Table tab, Pool pool, EsdfBox b, uint32_t min_weight, float min_prob,
+__global__ __launch_bounds__(512) void k_surface(Table tab, Pool pool, MapBox b, uint32_t min_weight, float min_prob,
                                                  float vs, uint32_t* __restrict__ cnt,
                                                  const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total,
                                                  uint4* __restrict__ out, long long capacity,
@@ -51,20 +51,16 @@ __global__ __launch_bounds__(512) void k_surface(Table tab, Pool pool, EsdfBox b
   }
   const int bx = b.bx0 + (int)(g % (uint32_t)b.nbx), by = b.by0 + (int)((g / (uint32_t)b.nbx) % (uint32_t)b.nby);
   const int bz = b.bz0 + (int)(g / ((uint32_t)b.nbx * (uint32_t)b.nby));
-  // (a pending entry, kPlaceholderIdx, names no pool block: absent; a neighbour beyond the int16 voxel range too)
-  auto probe = [&](int x, int y, int z) -> int32_t {
-    if (x < -4096 || x > 4095 || y < -4096 || y > 4095 || z < -4096 || z > 4095) return -1;
-    const uint32_t e0 = block_hash(x, y, z, tab.bucket_mask) << 1;
-    const int32_t r = sample_resolve(tab, x, y, z, e0, load_entry(tab.entries, e0), load_entry(tab.entries, e0 + 1));
-    return r < tab.num_block ? r : -1;
-  };
-  if (tid == 0) s_nb[13] = probe(bx, by, bz);
+  if (tid == 0) s_nb[13] = lookup_block(tab, bx, by, bz);  // (the box lies inside the grid: surface_box)
   lds_barrier();
   if (s_nb[13] < 0) {
     if (!kEmit && tid == 0) cnt[g] = 0u;
     return;
   }
-  if (tid < 27 && tid != 13) s_nb[tid] = probe(bx + tid % 3 - 1, by + tid / 3 % 3 - 1, bz + tid / 9 - 1);
+  if (tid < 27 && tid != 13) {  // (a neighbour beyond the grid is absent)
+    const int x = bx + tid % 3 - 1, y = by + tid / 3 % 3 - 1, z = bz + tid / 9 - 1;
+    s_nb[tid] = block_in_grid(x, y, z) ? lookup_block(tab, x, y, z) : -1;
+  }
   lds_barrier();
 
   constexpr int lo = kEmit ? -1 : 0, n = kEmit ? 11 : 9;

@@ -1,14 +1,8 @@
 // query.inc -- reading the map out: ratsdf_query and the gathers of valid blocks (voxel records, the marching-cubes
 // mesh), their file forms, and the ray cast.  Included at the end of ratsdf_engine.hip.  Every call settles first, selects
-// into the engine's `vis` buffer and copies out through buffers the engine keeps.
+// into the engine's `vis` buffer and copies out through the engine's staging pair (ratsdf_engine::staging).
 
 extern "C" {
-
-// Device and page-locked staging buffers of the query-side downloads: kept between calls and only
-// ever grown (a hipMalloc / hipFree pair and a pageable D2H copy per Query cost more than the kernels).
-static int ensure_download_buffers(ratsdf_engine* e, size_t bytes) {
-  return e->grow_pair(e->dl_dev, e->dl_host, bytes, bytes + bytes / 4);
-}
 
 static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t* n) {
   uint32_t cnt = 0;
@@ -21,13 +15,16 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
   void* host = malloc(total ? total * rec : 1);
   if (!host) return RATSDF_ERR_DEVICE;
   if (total) {
-    const int st = ensure_download_buffers(e, total * rec);
+    // the staging pair: a side that has to grow grows by a quarter more, so a map that gains a few blocks between
+    // gathers does not reallocate every time (a hipMalloc / hipFree pair per Query costs more than the kernels)
+    const size_t bytes = total * rec, more = bytes + bytes / 4;
+    const int st = e->staging(bytes <= e->d_out.size() ? bytes : more, bytes <= e->h_out.size() ? bytes : more);
     if (st != RATSDF_OK) {
       free(host);
       return st;
     }
-    float* dev = e->dl_dev.as<float>();
-    const uint8_t* dl_host = e->dl_host.as<uint8_t>();
+    float* dev = e->d_out.as<float>();
+    const uint8_t* h = e->h_out.as<uint8_t>();
     const unsigned grid = cnt < 4096u ? (cnt + 3) / 4 : 1024u;
     if (semantic)
       hipLaunchKernelGGL(k_download<true>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
@@ -35,7 +32,7 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
     else
       hipLaunchKernelGGL(k_download<false>, dim3(grid), dim3(256), 0, e->stream, e->pool, e->vis,
                          &e->ctl->n_sel, e->vs, dev);
-    hipError_t err = hipMemcpyAsync(e->dl_host.as<void>(), dev, total * rec, hipMemcpyDeviceToHost, e->stream);
+    hipError_t err = hipMemcpyAsync(e->h_out.as<void>(), dev, bytes, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (err != hipSuccess) {
       free(host);
@@ -44,17 +41,16 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
     // the caller owns `host` (ratsdf_free_buffer).  A large result is copied out by the engine's helper threads side
     // by side: the destination is fresh memory, and first-touch page faults (10 k of them for the 41 MB of a
     // GatherValid on the bench map) are what the single-threaded copy spent most of its time on
-    const size_t bytes = total * rec;
     HostCopyPool* cp = bytes >= ((size_t)4 << 20) ? e->host_copy_pool() : nullptr;
     if (cp) {
       HostCopyPool::Piece pieces[16];
       int np = 0;
       const size_t step = ((bytes + 15) / 16 + 4095) & ~(size_t)4095;
       for (size_t o = 0; o < bytes; o += step)
-        pieces[np++] = HostCopyPool::Piece{(uint8_t*)host + o, dl_host + o, std::min(step, bytes - o)};
+        pieces[np++] = HostCopyPool::Piece{(uint8_t*)host + o, h + o, std::min(step, bytes - o)};
       cp->copy(pieces, np);
     } else {
-      memcpy(host, dl_host, bytes);
+      memcpy(host, h, bytes);
     }
   }
   *out = host;
@@ -156,12 +152,12 @@ int ratsdf_raycast_rows(ratsdf_engine* e, const ratsdf_intrinsics* K, int height
   ENTRY(e, height > 0 && width > 0 && row0 >= 0 && row1 <= height && row0 <= row1);  // (K, T, max_depth: raycast_rows_device)
   const size_t bytes = (size_t)(row1 - row0) * width * 4;
   if (bytes == 0) return raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, nullptr, nullptr);
-  // The two images leave through buffers the engine keeps: device memory for the kernel's output and page-locked host
-  // memory for the copy out (until round 5: a hipMalloc / hipFree pair per call and two copies into the caller's
-  // pageable buffers through the runtime's staging path -- 0.84 ms per 640x480 rendering of which the kernel was half).
-  STCHK(e->grow_pair(e->d_render, e->h_render, bytes * 2, bytes * 2));
-  uint8_t* d = e->d_render.as<uint8_t>();
-  uint8_t* h = e->h_render.as<uint8_t>();
+  // The two images leave through the engine's staging pair, in one copy: device memory for the kernel's output and
+  // page-locked host memory for the copy out (until round 5: a hipMalloc / hipFree pair per call and two copies into the
+  // caller's pageable buffers through the runtime's staging path -- 0.84 ms per 640x480 rendering of which the kernel was half).
+  STCHK(e->staging(bytes * 2, bytes * 2));
+  uint8_t* d = e->d_out.as<uint8_t>();
+  uint8_t* h = e->h_out.as<uint8_t>();
   STCHK(raycast_rows_device(e, K, height, width, T, max_depth, row0, row1, d, d + bytes));
   HIPCHK(hipMemcpyAsync(h, d, bytes * 2, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));  // voxel_tsdf.cu:901
@@ -182,13 +178,14 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
   // check_valid_kernel + GatherBlock; a sharded map meshes the blocks it owns (imported neighbours are read only)
   STCHK(e->select(e->shard_count > 1 ? kSelOwned : kSelValid, GridBounds{}, &e->ctl->n_sel));
   uint32_t nb = 0;
-  HIPCHK(hipMemcpyAsync(&nb, &e->ctl->n_sel, 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  STCHK(e->read_small(&nb, &e->ctl->n_sel, 4));
+  // the caller owns the three arrays (ratsdf_free_buffer): placeholders while the mesh is empty or the call fails
   *vertices = (float*)malloc(4);
   *vertex_prob = (float*)malloc(4);
   *indices = (int32_t*)malloc(4);
   *n_vertices = 0;
   *n_triangles = 0;
+  if (!*vertices || !*vertex_prob || !*indices) return RATSDF_ERR_DEVICE;
   if (nb == 0) return RATSDF_OK;
   const size_t nvs = (size_t)nb * kVertVolume * 3;  // candidate vertices
   const size_t nts = (size_t)nb * 512 * 5;          // candidate triangles
@@ -202,7 +199,7 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
   // one scratch allocation: verts | vprob | vmask | vpos | tids | tmask | tpos | tile sums | total
   const size_t ntile_max = (nts > nvs ? nts : nvs) / kScanTile + 2;
   const size_t bytes = nvs * 12 + nvs * 4 * 3 + nts * 12 + nts * 4 * 2 + ntile_max * 4 + 64;
-  DevMem d, o;  // the scratch, and the compacted mesh on its way out
+  DevMem d;  // the scratch (the compacted mesh leaves through the staging pair)
   StreamDrain drain{e->stream};
   STCHK(d.alloc(bytes));
   float* verts = d.as<float>();
@@ -219,28 +216,26 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
   uint32_t nv = 0, nt = 0;
   STCHK(mask_positions(e, vmask, nvs, vpos, tiles, d_total, &nv));
   STCHK(mask_positions(e, tmask, nts, tpos, tiles, d_total, &nt));
-  free(*vertices);
-  free(*vertex_prob);
-  free(*indices);
-  *vertices = (float*)malloc((size_t)nv * 12 + 4);
-  *vertex_prob = (float*)malloc((size_t)nv * 4 + 4);
-  *indices = (int32_t*)malloc((size_t)nt * 12 + 4);
-  STCHK(o.alloc((size_t)nv * 16 + (size_t)nt * 12 + 64));
-  float* ov = o.as<float>();
+  const size_t out_bytes = (size_t)nv * 16 + (size_t)nt * 12 + 64;
+  STCHK(e->staging(out_bytes, std::min(out_bytes, kHostChunk)));
+  float* ov = e->d_out.as<float>();
   float* op = ov + (size_t)nv * 3;
   int32_t* oi = (int32_t*)(op + nv);
   hipLaunchKernelGGL(k_compact_vertices, dim3(2048), dim3(256), 0, e->stream, verts, vprob, vmask,
                      vpos, nvs, ov, op);
   hipLaunchKernelGGL(k_compact_triangles, dim3(2048), dim3(256), 0, e->stream, tids, tmask, tpos,
                      vpos, nts, oi);
-  hipError_t err = hipSuccess;
-  if (nv) err = hipMemcpyAsync(*vertices, ov, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess && nv)
-    err = hipMemcpyAsync(*vertex_prob, op, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess && nt)
-    err = hipMemcpyAsync(*indices, oi, (size_t)nt * 12, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  if (err != hipSuccess) return RATSDF_ERR_DEVICE;
+  HIPCHK(hipGetLastError());
+  void* const hv = realloc(*vertices, (size_t)nv * 12 + 4);  // (a failed realloc leaves the placeholder)
+  void* const hp = realloc(*vertex_prob, (size_t)nv * 4 + 4);
+  void* const hi = realloc(*indices, (size_t)nt * 12 + 4);
+  if (hv) *vertices = (float*)hv;
+  if (hp) *vertex_prob = (float*)hp;
+  if (hi) *indices = (int32_t*)hi;
+  if (!hv || !hp || !hi) return RATSDF_ERR_DEVICE;
+  STCHK(e->download(hv, ov, (size_t)nv * 12));
+  STCHK(e->download(hp, op, (size_t)nv * 4));
+  STCHK(e->download(hi, oi, (size_t)nt * 12));
   *n_vertices = nv;
   *n_triangles = nt;
   return RATSDF_OK;

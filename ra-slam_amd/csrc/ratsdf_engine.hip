@@ -236,21 +236,14 @@ class HostCopyPool {
 struct EngineMem {
   std::vector<DevMem> fixed, pix_mem, rank_mem;
   HostMem h_err_page;  // (ratsdf_engine::h_err)
-  DevMem d_render;     // ray casting through the host entry points: output, and its page-locked copy
-  HostMem h_render;
-  DevMem d_sample;     // point sampling through the host entry point: records | points, and the page-locked copy
-  HostMem h_sample;
+  DevMem d_out;        // results on their way to the caller's host memory, and the page-locked buffer they pass
+  HostMem h_out;       // through: ONE pair for every host-result entry point (ratsdf_engine::staging / download)
   DevMem d_esdf;       // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks (ratsdf_engine::esdf_cap)
-  HostMem h_esdf;      // page-locked copy of the host entry point's results, passed through in chunks
   DevMem d_surface;    // surface-point workspace (ratsdf_surface_points*): counts | starts | tile sums | total
                        // (ratsdf_engine::surface_cap)
-  DevMem d_surface_pts;  // the host entry point's records on the device, and their page-locked pass-through
-  HostMem h_surface;
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
-  DevMem dl_dev;       // query-side downloads (grow-only)
-  HostMem dl_host;
   HostMem h_stage;     // staging ring of the host-image entry points (ratsdf_engine::stage_pix)
   DevMem d_stage;
 
@@ -353,7 +346,8 @@ struct ratsdf_engine : EngineMem {
   Pool pool{};
   Ctl* ctl = nullptr;
   ratsdf_frame_stats* d_stats = nullptr;
-  int grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes);
+  int staging(size_t dev_bytes, size_t host_bytes);
+  int download(void* dst, const void* d_src, size_t bytes);
   size_t esdf_cap = 0;        // voxels the ESDF workspace was laid out for
   size_t surface_cap = 0;     // cells of the block grid the surface-point workspace was laid out for
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
@@ -759,15 +753,40 @@ int ratsdf_engine::stage_fail(int status) {
   return status;
 }
 
-// A device buffer and its page-locked twin, regrown together (to `bytes`) when either holds less than `need`; the
-// stream is drained first: what it has queued may still use the old ones.
-int ratsdf_engine::grow_pair(DevMem& d, HostMem& h, size_t need, size_t bytes) {
-  if (need <= d.size() && need <= h.size()) return RATSDF_OK;
-  HIPCHK(hipStreamSynchronize(stream));
-  d.reset();
-  h.reset();
-  STCHK(d.alloc(bytes));
-  return h.alloc(bytes);
+constexpr size_t kHostChunk = (size_t)32 << 20;  // bytes of h_out that a result of any size passes through
+
+// The staging pair of the host-result entry points: d_out holds at least `dev_bytes` and h_out at least `host_bytes`
+// afterwards.  Such an entry point returns only after its result has been copied out and the stream has drained, and
+// the entry points of a handle are serialised, so one pair serves them all; what an earlier call left in it is dead.
+// Grow-only, each side on its own; the stream is drained before a side is replaced (what it has queued may still use
+// the old one), and a side that failed to grow is empty (hip_mem.h).
+int ratsdf_engine::staging(size_t dev_bytes, size_t host_bytes) {
+  if (dev_bytes > d_out.size()) {
+    HIPCHK(hipStreamSynchronize(stream));
+    STCHK(d_out.alloc(dev_bytes));
+  }
+  if (host_bytes > h_out.size()) {
+    HIPCHK(hipStreamSynchronize(stream));
+    STCHK(h_out.alloc(host_bytes));
+  }
+  return RATSDF_OK;
+}
+
+// `bytes` of device memory into the caller's pageable `dst`, after everything enqueued so far: through h_out, in
+// pieces of what it holds (staging() in front sizes it; kHostChunk is enough for any result), each piece waited for
+// before it is copied on -- not straight into pageable memory, which is the runtime's staging path (read_small).
+// Returns with the stream drained; after a HIP error nothing further has been copied.
+int ratsdf_engine::download(void* dst, const void* d_src, size_t bytes) {
+  const size_t step = h_out.size();
+  if (bytes && !step) return RATSDF_ERR_DEVICE;
+  for (size_t o = 0; o < bytes; o += step) {
+    const size_t m = std::min(step, bytes - o);
+    HIPCHK(hipMemcpyAsync(h_out.as<void>(), (const uint8_t*)d_src + o, m, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    memcpy((uint8_t*)dst + o, h_out.as<void>(), m);
+  }
+  if (!bytes) HIPCHK(hipStreamSynchronize(stream));
+  return RATSDF_OK;
 }
 
 CarveBufs ratsdf_engine::carve_bufs(unsigned par) const {

@@ -3,7 +3,7 @@
 
 extern "C" {
 
-constexpr size_t kSampleChunk = (size_t)1 << 21;  // points per staged pass of the host entry point (88 MiB of buffers)
+constexpr size_t kSampleChunk = (size_t)1 << 21;  // points per staged pass of the host entry point (88 MiB a side)
 constexpr size_t kSampleRecord = 32, kSamplePoint = 12;
 
 static int sample_launch(ratsdf_engine* e, const float* d_xyz, size_t n, void* d_out) {
@@ -26,16 +26,14 @@ int ratsdf_sample_points(ratsdf_engine* e, const float* xyz, size_t n, ratsdf_sa
   ENTRY(e, (n == 0 || (xyz && out)) && n <= (size_t)INT32_MAX);
   STCHK(e->settle());
   if (n == 0) return e->sticky();
-  // points in and records out through buffers the engine keeps, grown on demand (as the ray cast's d_render /
-  // h_render); their capacity in points is what they hold
+  // points in and records out through the engine's staging pair, both sides laid out records | points for the chunk
+  // asked for (the pair may hold more, and its sides may differ: other calls grow it too)
   const size_t chunk = std::min(n, kSampleChunk);
-  const size_t per = kSampleRecord + kSamplePoint;
-  STCHK(e->grow_pair(e->d_sample, e->h_sample, chunk * per, chunk * per));
-  const size_t cap = e->d_sample.size() / per;
-  uint8_t* d_rec = e->d_sample.as<uint8_t>();
-  float* d_pts = (float*)(d_rec + cap * kSampleRecord);
-  uint8_t* h_rec = e->h_sample.as<uint8_t>();
-  float* h_pts = (float*)(h_rec + cap * kSampleRecord);
+  STCHK(e->staging(chunk * (kSampleRecord + kSamplePoint), chunk * (kSampleRecord + kSamplePoint)));
+  uint8_t* d_rec = e->d_out.as<uint8_t>();
+  float* d_pts = (float*)(d_rec + chunk * kSampleRecord);
+  uint8_t* h_rec = e->h_out.as<uint8_t>();
+  float* h_pts = (float*)(h_rec + chunk * kSampleRecord);
   for (size_t o = 0; o < n; o += chunk) {
     const size_t m = std::min(chunk, n - o);
     memcpy(h_pts, xyz + 3 * o, m * kSamplePoint);

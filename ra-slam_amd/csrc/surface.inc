@@ -6,8 +6,6 @@ extern "C" {
 static_assert(sizeof(ratsdf_surface_point) == 32 && offsetof(ratsdf_surface_point, prob) == 24,
               "ratsdf_surface_point layout");
 
-constexpr size_t kSurfaceHostChunk = (size_t)32 << 20;  // bytes of the host entry point's page-locked pass-through
-
 // the workspace of a box of n cells of the block grid: points per cell (4n B) | where each cell's points start (4n B) |
 // the scan's tile sums | the total (a word) and the host entry point's int64 count, 16 bytes together
 struct SurfaceWork {
@@ -18,14 +16,13 @@ static size_t surface_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; 
 static size_t surface_work_bytes(size_t n) { return 2 * esdf_round(4 * n) + esdf_round(4 * surface_tiles(n)) + 16; }
 
 // argument checks of both entry points (RATSDF_ERR_BAD_ARGUMENT when false); *ncells: cells of the box's block grid
-static bool surface_box(const int32_t* origin, const int32_t* dims, const ratsdf_surface_params* p, EsdfBox* b,
+static bool surface_box(const int32_t* origin, const int32_t* dims, const ratsdf_surface_params* p, MapBox* b,
                         size_t* ncells) {
   size_t n = 0;
   if (!p || p->min_weight < 1 || p->min_weight > 255 || std::isnan(p->min_prob) || p->flags || p->reserved ||
       !esdf_box(origin, dims, 0.f, 0u, b, &n))
     return false;
-  const int nbz = ((b->oz + b->Z - 1) >> 3) - b->bz0 + 1;
-  *ncells = (size_t)b->nbx * (size_t)b->nby * (size_t)nbz;
+  *ncells = box_cells(*b);
   return true;
 }
 
@@ -48,7 +45,7 @@ static int surface_workspace(ratsdf_engine* e, size_t n, SurfaceWork* w) {
 }
 
 // the count pass and the scan: points per cell, where each cell's points start, the total (no more than 3 * 2^27)
-static int surface_count(ratsdf_engine* e, const EsdfBox& b, size_t ncells, const ratsdf_surface_params& p,
+static int surface_count(ratsdf_engine* e, const MapBox& b, size_t ncells, const ratsdf_surface_params& p,
                          const SurfaceWork& w) {
   hipLaunchKernelGGL(k_surface<false>, dim3((unsigned)ncells), dim3(512), 0, e->stream, e->tab, e->pool, b,
                      (uint32_t)p.min_weight, p.min_prob, e->vs, w.cnt, (const uint32_t*)nullptr,
@@ -63,7 +60,7 @@ static int surface_count(ratsdf_engine* e, const EsdfBox& b, size_t ncells, cons
 }
 
 // the emit pass: the first min(total, capacity) points, and the total as an int64 at d_count
-static int surface_emit(ratsdf_engine* e, const EsdfBox& b, size_t ncells, const ratsdf_surface_params& p,
+static int surface_emit(ratsdf_engine* e, const MapBox& b, size_t ncells, const ratsdf_surface_params& p,
                         const SurfaceWork& w, void* d_points, int64_t capacity, void* d_count) {
   hipLaunchKernelGGL(k_surface<true>, dim3((unsigned)ncells), dim3(512), 0, e->stream, e->tab, e->pool, b,
                      (uint32_t)p.min_weight, p.min_prob, e->vs, w.cnt, (const uint32_t*)w.pos,
@@ -75,7 +72,7 @@ static int surface_emit(ratsdf_engine* e, const EsdfBox& b, size_t ncells, const
 int ratsdf_surface_points_device(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3],
                                  const ratsdf_surface_params* params, void* d_points, int64_t capacity,
                                  void* d_count) {
-  EsdfBox b;
+  MapBox b;
   size_t ncells = 0;
   ENTRY(e, capacity >= 0 && (d_points || capacity == 0) && !((uintptr_t)d_points & 15u) && d_count &&
                !((uintptr_t)d_count & 7u) && surface_box(origin, dims, params, &b, &ncells));
@@ -89,7 +86,7 @@ int ratsdf_surface_points_device(ratsdf_engine* e, const int32_t origin[3], cons
 
 int ratsdf_surface_points(ratsdf_engine* e, const int32_t origin[3], const int32_t dims[3],
                           const ratsdf_surface_params* params, ratsdf_surface_point** out, size_t* n) {
-  EsdfBox b;
+  MapBox b;
   size_t ncells = 0;
   ENTRY(e, out && n && surface_box(origin, dims, params, &b, &ncells));
   STCHK(e->settle());
@@ -103,27 +100,12 @@ int ratsdf_surface_points(ratsdf_engine* e, const int32_t origin[3], const int32
   *n = 0;
   if (total == 0u) return e->sticky();
   const size_t bytes = (size_t)total * sizeof(ratsdf_surface_point);
-  STCHK(e->d_surface_pts.grow(bytes));  // (nothing queued uses it: the stream has just been drained)
-  STCHK(e->h_surface.grow(kSurfaceHostChunk));
-  STCHK(surface_emit(e, b, ncells, *params, w, e->d_surface_pts.as<void>(), (int64_t)total, w.count));
-  uint8_t* host = (uint8_t*)malloc(bytes);
-  if (!host) {
-    (void)hipStreamSynchronize(e->stream);
-    return RATSDF_ERR_DEVICE;
-  }
-  uint8_t* const h = e->h_surface.as<uint8_t>();
-  const uint8_t* const d = e->d_surface_pts.as<uint8_t>();
-  for (size_t o = 0; o < bytes; o += kSurfaceHostChunk) {
-    const size_t m = std::min(kSurfaceHostChunk, bytes - o);
-    hipError_t err = hipMemcpyAsync(h, d + o, m, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) {
-      free(host);
-      return RATSDF_ERR_DEVICE;
-    }
-    memcpy(host + o, h, m);
-  }
-  const int st = e->sticky();
+  STCHK(e->staging(bytes, kHostChunk));
+  void* host = malloc(bytes);
+  if (!host) return RATSDF_ERR_DEVICE;  // (nothing is queued: read_small drained the stream)
+  int st = surface_emit(e, b, ncells, *params, w, e->d_out.as<void>(), (int64_t)total, w.count);
+  if (st == RATSDF_OK) st = e->download(host, e->d_out.as<void>(), bytes);
+  if (st == RATSDF_OK) st = e->sticky();
   if (st != RATSDF_OK) {
     free(host);
     return st;

@@ -2,7 +2,8 @@
 """Timings of the query-side entry points on the bench map, HIP engine vs
 the CPU oracle (16 threads): tools/aux_bench.py  (GPU box).  The last leg times the surface points
 (include/ratsdf_surface.h) beside the mesh export and the host route on the same map; `--surface` runs that leg and
-the mesh export alone (no oracle)."""
+the mesh export alone (no oracle); `--no-oracle` runs every row on the HIP engine alone (a same-box A/B of two
+libraries, RATSDF_LIB, needs no CPU column)."""
 import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -17,7 +18,7 @@ from oracle_binding import load_oracle
 vs, md = 0.005, 4.0
 gpu = ratsdf.TSDFGrid(vs, 6 * vs)
 only_surface = "--surface" in sys.argv
-cpu = None if only_surface else Engine(load_oracle(), vs, 6 * vs, threads=16)
+cpu = None if only_surface or "--no-oracle" in sys.argv else Engine(load_oracle(), vs, 6 * vs, threads=16)
 frames = [synthetic.frame("room", i, noise=True, holes=True) for i in range(45)]
 for f in frames:
     for e in (gpu, cpu) if cpu else (gpu,):
