@@ -29,6 +29,30 @@ namespace ratsdf {
 
 constexpr int kSurfRow = 24, kSurfPlane = 11 * kSurfRow, kSurfVolume = 11 * kSurfPlane;
 
+// d_b(w) of the header for the voxel at LDS index w, sb: the stride of axis b
+__device__ inline float surface_diff(const float* s_t, const uint8_t* s_obs, int w, int sb) {
+  const bool up = s_obs[w + sb] != 0, dn = s_obs[w - sb] != 0;
+  const float tu = s_t[w + sb], td = s_t[w - sb], tw = s_t[w];
+  return up && dn ? (tu - td) * 0.5f : up ? tu - tw : dn ? tw - td : 0.f;
+}
+// Position and normal of the crossing on edge (the voxel at LDS index c, axis a) with factor f, as the header writes
+// them: r[0 .. 2] pos, r[3 .. 5] normal.  d0: d_b of the owner; vf: its voxel index.  The one place this arithmetic
+// lives: k_surface and k_surface_mesh (kernels_surface_mesh.h) write the same bytes.
+__device__ inline void surface_pos_normal(const float* s_t, const uint8_t* s_obs, int c, int a, float f,
+                                          const float (&d0)[3], const float (&vf)[3], float vs, float (&r)[6]) {
+  const int st = a == 0 ? 1 : a == 1 ? kSurfRow : kSurfPlane;
+  const float u = 1.f - f;
+  const float g0 = d0[0] * u + surface_diff(s_t, s_obs, c + st, 1) * f;
+  const float g1 = d0[1] * u + surface_diff(s_t, s_obs, c + st, kSurfRow) * f;
+  const float g2 = d0[2] * u + surface_diff(s_t, s_obs, c + st, kSurfPlane) * f;
+  const float len = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
+  const bool flat = len == 0.f || !(fabsf(len) < INFINITY);  // 0, infinite or NaN
+  r[3] = flat ? 0.f : g0 / len, r[4] = flat ? 0.f : g1 / len, r[5] = flat ? 0.f : g2 / len;
+  r[0] = (a == 0 ? vf[0] + f : vf[0]) * vs;
+  r[1] = (a == 1 ? vf[1] + f : vf[1]) * vs;
+  r[2] = (a == 2 ? vf[2] + f : vf[2]) * vs;
+}
+
 // cnt: points per cell (written by the count pass, read by the emit pass); pos / total: the scan's results; out: 2
 // uint4 per point (the 32-byte ratsdf_surface_point)
 template <bool kEmit>
@@ -115,33 +139,20 @@ __global__ __launch_bounds__(512) void k_surface(Table tab, Pool pool, MapBox b,
     return;
   }
   if (mine == 0u) return;
-  // d_b(w) of the header for the voxel at LDS index w, sb: the stride of axis b
-  auto diff = [&](int w, int sb) -> float {
-    const bool up = s_obs[w + sb] != 0, dn = s_obs[w - sb] != 0;
-    const float tu = s_t[w + sb], td = s_t[w - sb], tw = s_t[w];
-    return up && dn ? (tu - td) * 0.5f : up ? tu - tw : dn ? tw - td : 0.f;
-  };
-  const float d0[3] = {diff(c, 1), diff(c, kSurfRow), diff(c, kSurfPlane)};
+  const float d0[3] = {surface_diff(s_t, s_obs, c, 1), surface_diff(s_t, s_obs, c, kSurfRow),
+                       surface_diff(s_t, s_obs, c, kSurfPlane)};
   const float vf[3] = {(float)vx, (float)vy, (float)vz};
   long long o = (long long)first + (long long)at;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     if (!cr[a]) continue;
-    const int st = a == 0 ? 1 : a == 1 ? kSurfRow : kSurfPlane;
-    const float u = 1.f - f[a];
-    const float g0 = d0[0] * u + diff(c + st, 1) * f[a];
-    const float g1 = d0[1] * u + diff(c + st, kSurfRow) * f[a];
-    const float g2 = d0[2] * u + diff(c + st, kSurfPlane) * f[a];
-    const float len = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
-    const bool flat = len == 0.f || !(fabsf(len) < INFINITY);  // 0, infinite or NaN
-    const float n0 = flat ? 0.f : g0 / len, n1 = flat ? 0.f : g1 / len, n2 = flat ? 0.f : g2 / len;
-    const float p0 = (a == 0 ? vf[0] + f[a] : vf[0]) * vs;
-    const float p1 = (a == 1 ? vf[1] + f[a] : vf[1]) * vs;
-    const float p2 = (a == 2 ? vf[2] + f[a] : vf[2]) * vs;
+    float r[6];
+    surface_pos_normal(s_t, s_obs, c, a, f[a], d0, vf, vs, r);
     if (o < capacity) {
       const uint32_t colour = pool.rgbw[pv[a]];
-      out[2 * (size_t)o] = make_uint4(__float_as_uint(p0), __float_as_uint(p1), __float_as_uint(p2), __float_as_uint(n0));
-      out[2 * (size_t)o + 1] = make_uint4(__float_as_uint(n1), __float_as_uint(n2), __float_as_uint(prob[a]), colour);
+      out[2 * (size_t)o] = make_uint4(__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]),
+                                      __float_as_uint(r[3]));
+      out[2 * (size_t)o + 1] = make_uint4(__float_as_uint(r[4]), __float_as_uint(r[5]), __float_as_uint(prob[a]), colour);
     }
     ++o;
   }

@@ -165,6 +165,9 @@ class TSDFSystem {
   // TSDFGrid::SurfacePoints under the engine's mutex, like Sample
   int SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
                     std::vector<ratsdf_surface_point>* out);
+  // TSDFGrid::SurfaceMesh under the engine's mutex, like Sample
+  int SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
+                  std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

@@ -20,6 +20,7 @@
 #include "../../../../include/ratsdf_coarsen.h"
 #include "../../../../include/ratsdf_esdf.h"
 #include "../../../../include/ratsdf_surface.h"
+#include "../../../../include/ratsdf_surface_mesh.h"
 
 namespace ratsdf {
 

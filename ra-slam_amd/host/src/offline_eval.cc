@@ -26,6 +26,11 @@
 //          [--surface-points FILE (after the last frame: the oriented surface points of the map's bounding box,
 //          32-byte records of include/ratsdf_surface.h, min_weight 1; a box beyond 512 voxels along an axis is
 //          covered by block-aligned boxes of at most 512, z then y then x, each in the header's order)]
+//          [--surface-mesh FILE.ply (after the last frame: the welded triangle mesh of the map's bounding box,
+//          include/ratsdf_surface_mesh.h, min_weight 1, as one binary little-endian PLY -- vertices x y z nx ny nz
+//          (float), red green blue (uchar), prob (float), weight (uchar); faces as lists of three int indices.  The box
+//          is tiled as for --surface-points; each tile's mesh is self-contained, so the vertices on a face two tiles
+//          share are written once per tile: duplicates there are accepted)]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -52,18 +57,24 @@ void write_file(const std::string& path, const void* data, size_t bytes) {
   }
 }
 
-// the oriented surface points of the map's bounding box (include/ratsdf_surface.h) as a file of records
-int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
+// the block-aligned bounding box of the map's voxels, lo .. hi inclusive; false when the map is empty
+bool map_bounds(TSDFSystem& tsdf, float vs, int lo[3], int hi[3]) {
   const float far = 32000.f * vs;  // (every voxel index the directory can hold lies within +-32768)
   const std::vector<VoxelSpatialTSDF> vox = tsdf.Query(BoundingCube<float>{-far, far, -far, far, -far, far});
+  for (int a = 0; a < 3; ++a) lo[a] = 32767, hi[a] = -32768;
+  for (const VoxelSpatialTSDF& v : vox) {
+    const int idx[3] = {(int)lrintf(v.x / vs), (int)lrintf(v.y / vs), (int)lrintf(v.z / vs)};
+    for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], idx[a]), hi[a] = std::max(hi[a], idx[a]);
+  }
+  for (int a = 0; a < 3; ++a) lo[a] = std::max(lo[a] & ~7, -32768), hi[a] = std::min(hi[a] | 7, 32767);  // whole blocks
+  return !vox.empty();
+}
+
+// the oriented surface points of the map's bounding box (include/ratsdf_surface.h) as a file of records
+int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
   std::vector<ratsdf_surface_point> all, part;
-  if (!vox.empty()) {
-    int lo[3] = {32767, 32767, 32767}, hi[3] = {-32768, -32768, -32768};
-    for (const VoxelSpatialTSDF& v : vox) {
-      const int idx[3] = {(int)lrintf(v.x / vs), (int)lrintf(v.y / vs), (int)lrintf(v.z / vs)};
-      for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], idx[a]), hi[a] = std::max(hi[a], idx[a]);
-    }
-    for (int a = 0; a < 3; ++a) lo[a] = std::max(lo[a] & ~7, -32768), hi[a] = std::min(hi[a] | 7, 32767);  // whole blocks
+  int lo[3], hi[3];
+  if (map_bounds(tsdf, vs, lo, hi)) {
     ratsdf_surface_params params;
     memset(&params, 0, sizeof(params));
     params.min_weight = 1;
@@ -80,6 +91,60 @@ int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
   }
   write_file(path, all.data(), all.size() * sizeof(ratsdf_surface_point));
   fprintf(stderr, "[offline_eval] %zu surface points to %s\n", all.size(), path.c_str());
+  return RATSDF_OK;
+}
+
+// the welded triangle mesh of the map's bounding box (include/ratsdf_surface_mesh.h) as a binary little-endian PLY;
+// tiled exactly as write_surface_points tiles, each tile's indices offset by the vertices written before it
+int write_surface_mesh(TSDFSystem& tsdf, float vs, const std::string& path) {
+  std::vector<ratsdf_surface_point> vertices, part_v;
+  std::vector<int32_t> triangles, part_t;
+  int lo[3], hi[3];
+  if (map_bounds(tsdf, vs, lo, hi)) {
+    ratsdf_surface_mesh_params params;
+    memset(&params, 0, sizeof(params));
+    params.min_weight = 1;
+    for (int z = lo[2]; z <= hi[2]; z += 512)
+      for (int y = lo[1]; y <= hi[1]; y += 512)
+        for (int x = lo[0]; x <= hi[0]; x += 512) {
+          const int32_t origin[3] = {x, y, z};
+          const int32_t dims[3] = {std::min(512, hi[0] - x + 1), std::min(512, hi[1] - y + 1),
+                                   std::min(512, hi[2] - z + 1)};
+          const int st = tsdf.SurfaceMesh(origin, dims, params, &part_v, &part_t);
+          if (st != RATSDF_OK) return st;
+          if (vertices.size() + part_v.size() > (size_t)INT32_MAX) return RATSDF_ERR_BAD_ARGUMENT;  // (int indices)
+          const int32_t base = (int32_t)vertices.size();
+          vertices.insert(vertices.end(), part_v.begin(), part_v.end());
+          for (const int32_t i : part_t) triangles.push_back(base + i);
+        }
+  }
+  const size_t nv = vertices.size(), nt = triangles.size() / 3;
+  char header[512];
+  const int hn = snprintf(header, sizeof(header),
+                          "ply\nformat binary_little_endian 1.0\ncomment ratsdf surface mesh, voxel size %g\n"
+                          "element vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                          "property float nx\nproperty float ny\nproperty float nz\n"
+                          "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                          "property float prob\nproperty uchar weight\n"
+                          "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
+                          vs, nv, nt);
+  std::vector<uint8_t> file((size_t)hn + nv * 32 + nt * 13);
+  uint8_t* p = file.data();
+  memcpy(p, header, (size_t)hn), p += hn;
+  for (const ratsdf_surface_point& v : vertices) {  // 24 + 3 + 4 + 1 bytes: the record, colour before probability
+    memcpy(p, v.pos, 12), memcpy(p + 12, v.normal, 12);
+    p[24] = v.rgbw.r, p[25] = v.rgbw.g, p[26] = v.rgbw.b;
+    memcpy(p + 27, &v.prob, 4);
+    p[31] = v.rgbw.weight;
+    p += 32;
+  }
+  for (size_t i = 0; i < nt; ++i) {
+    *p = 3;
+    memcpy(p + 1, &triangles[3 * i], 12);
+    p += 13;
+  }
+  write_file(path, file.data(), file.size());
+  fprintf(stderr, "[offline_eval] %zu vertices, %zu triangles to %s\n", nv, nt, path.c_str());
   return RATSDF_OK;
 }
 
@@ -114,6 +179,7 @@ int main(int argc, char** argv) {
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
   std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points, save_coarse_map;
+  std::string surface_mesh;
   int coarse_levels = 1;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
@@ -140,6 +206,7 @@ int main(int argc, char** argv) {
     else if (a == "--save-map") save_map = next();
     else if (a == "--fuse-map") fuse_map = next();
     else if (a == "--surface-points") surface_points = next();
+    else if (a == "--surface-mesh") surface_mesh = next();
     else if (a == "--save-coarse-map") save_coarse_map = next();
     else if (a == "--coarse-levels") coarse_levels = atoi(next());
     else if (a == "--first-frame") first_frame = atoi(next());
@@ -266,6 +333,14 @@ int main(int argc, char** argv) {
         const int st = write_surface_points(*tsdf, voxel_size, surface_points);
         if (st != RATSDF_OK) {
           fprintf(stderr, "[offline_eval] --surface-points %s: %s\n", surface_points.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
+      if (!surface_mesh.empty()) {
+        const int st = write_surface_mesh(*tsdf, voxel_size, surface_mesh);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --surface-mesh %s: %s\n", surface_mesh.c_str(),
                   Api::Load(lib).status_string(st));
           return 1;
         }

@@ -85,6 +85,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.fuse_map_coarsened = reinterpret_cast<decltype(api.fuse_map_coarsened)>(opt_sym("fuse_map_coarsened"));
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
+  api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -293,6 +294,26 @@ int TSDFGrid::SurfacePoints(const int32_t origin[3], const int32_t dims[3], cons
     out->assign(buf, buf + n);
     api_->free_buffer(buf);
   }
+  return status_;
+}
+
+int TSDFGrid::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
+                          std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
+  if (vertices) vertices->clear();
+  if (triangles) triangles->clear();
+  if (!engine_ || !vertices || !triangles) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_surface_point* v = nullptr;
+  int32_t* t = nullptr;
+  size_t nv = 0, nt = 0;
+  note(api_->surface_mesh ? api_->surface_mesh(engine_, origin, dims, &params, &v, &nv, &t, &nt)
+                          : RATSDF_ERR_NOT_IMPLEMENTED,
+       "SurfaceMesh");
+  if (status_ == RATSDF_OK) {
+    if (v) vertices->assign(v, v + nv);
+    if (t) triangles->assign(t, t + 3 * nt);
+  }
+  if (v) api_->free_buffer(v);
+  if (t) api_->free_buffer(t);
   return status_;
 }
 
@@ -607,6 +628,12 @@ int TSDFSystem::SurfacePoints(const int32_t origin[3], const int32_t dims[3], co
                               std::vector<ratsdf_surface_point>* out) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.SurfacePoints(origin, dims, params, out);
+}
+
+int TSDFSystem::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
+                            std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.SurfaceMesh(origin, dims, params, vertices, triangles);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

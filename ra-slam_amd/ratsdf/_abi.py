@@ -115,6 +115,16 @@ class SurfaceParams(C.Structure):
     _fields_ = [("min_weight", C.c_int32), ("min_prob", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# include/ratsdf_surface_mesh.h (welded triangle mesh of a box): handled like SURFACE_SYMBOLS
+SURFACE_MESH_SYMBOLS = ["surface_mesh", "surface_mesh_device"]
+
+
+class SurfaceMeshParams(C.Structure):
+    """ratsdf_surface_mesh_params"""
+    _fields_ = [("min_weight", C.c_int32), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved1", C.c_uint32)]
+
+
 class _OwnedBuffer:
     """a result buffer handed over by the library (malloc'ed there): exposes it through the array interface and gives
     it back with ratsdf_free_buffer when the last array built on it is collected"""
@@ -253,6 +263,17 @@ class Library:
                 box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(SurfaceParams)]
                 f.argtypes = box + {"surface_points": [C.POINTER(vp), C.POINTER(C.c_size_t)],
                                     "surface_points_device": [vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in SURFACE_MESH_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(SurfaceMeshParams)]
+                f.argtypes = box + {"surface_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                                     C.POINTER(C.c_size_t)],
+                                    "surface_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
             self.fn[s] = f
 
         for s in FUSE_SYMBOLS:
@@ -686,6 +707,37 @@ class Engine:
             return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
         if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
             return int(d_count.numpy().view(np.int64).reshape(-1)[0])
+        return None                          # a raw pointer: the caller reads it
+
+    def surface_mesh(self, origin, dims, min_weight=1):
+        """welded triangle mesh of a box of voxels (ratsdf_surface_mesh, include/ratsdf_surface_mesh.h): (vertices,
+        triangles).  The vertices are SURFACE_DTYPE records, the surface points that the triangles of the box's
+        complete cells use, each once, in surface_points' order; the triangles are int32 [n, 3] indices into them,
+        wound so that their normal points into free space, in the order of their cell's voxel."""
+        pv, pt, nv, nt = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        params = SurfaceMeshParams(int(min_weight), 0, 0, 0)
+        _check(self.lib.fn["surface_mesh"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                           C.byref(pv), C.byref(nv), C.byref(pt), C.byref(nt)), "surface_mesh")
+        return self._take(pv, nv.value, SURFACE_DTYPE), self._take(pt, nt.value * 3, np.dtype("<i4")).reshape(-1, 3)
+
+    def surface_mesh_device(self, origin, dims, d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts,
+                            min_weight=1):
+        """surface_mesh() into DEVICE buffers, asynchronous on the engine's stream: the first min(total, capacity)
+        32-byte vertex records to d_vertices (16-byte aligned) and index triples to d_triangles (0 with capacity 0
+        for a pure count), and the true totals as two int64 (vertices, triangles) to d_counts.  A triangle written
+        while one of its vertices fell beyond vertex_capacity keeps its true index.  Each buffer: a torch tensor, a
+        devmem.DeviceArray or a raw pointer.  Returns the two totals (this waits for the stream)."""
+        params = SurfaceMeshParams(int(min_weight), 0, 0, 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_vertices, d_triangles, d_counts)]
+        _check(self.lib.fn["surface_mesh_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
+                                                  C.byref(params), ptr[0] or None, int(vertex_capacity),
+                                                  ptr[1] or None, int(triangle_capacity), ptr[2] or None),
+               "surface_mesh_device")
+        self.synchronize()
+        if hasattr(d_counts, "cpu"):         # a torch tensor
+            return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])
+        if hasattr(d_counts, "numpy"):       # a devmem.DeviceArray
+            return tuple(int(v) for v in d_counts.numpy().view(np.int64).reshape(-1)[:2])
         return None                          # a raw pointer: the caller reads it
 
     def gather_valid_mesh(self):
