@@ -55,7 +55,8 @@ def surface_mesh(blocks, origin, dims, vs, min_weight=1):
     # every crossing whose owner lies in [origin, origin + dims], in the header's order: surface_ref's records
     # (voxel 32768 does not exist: it owns nothing)
     n1 = np.minimum(dims + 1, 32768 - origin)
-    points = sr.surface_points(blocks, origin, n1, vs, min_weight, 0.0)
+    # (the mesh has no min_prob: -inf drops nothing, where 0.0 would drop a vertex of negative probability)
+    points = sr.surface_points(blocks, origin, n1, vs, min_weight, -np.inf)
     zero = np.zeros(3, dtype=np.int64)
     own, axis, vert = [], [], []
     for a in range(3):
