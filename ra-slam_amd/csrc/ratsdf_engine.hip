@@ -24,6 +24,7 @@
 #include "kernels_esdf.h"
 #include "kernels_surface.h"
 #include "kernels_surface_mesh.h"
+#include "kernels_regions.h"
 #include "kernels_fuse.h"
 #include "kernels_resample.h"
 #include "kernels_coarsen.h"
@@ -32,6 +33,7 @@
 #include "../../include/ratsdf_esdf.h"
 #include "../../include/ratsdf_surface.h"
 #include "../../include/ratsdf_surface_mesh.h"
+#include "../../include/ratsdf_regions.h"
 
 static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
 
@@ -246,6 +248,8 @@ struct EngineMem {
   DevMem d_surface_mesh;      // surface-mesh workspace (ratsdf_surface_mesh*): counts | starts | tile sums | totals |
                               // vertex codes (ratsdf_engine::surface_mesh_cap)
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
+  DevMem d_regions;    // region workspace (ratsdf_regions*): seed bytes | labels | ranks | tile sums | total
+                       // (ratsdf_engine::regions_cap)
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
@@ -356,6 +360,7 @@ struct ratsdf_engine : EngineMem {
   size_t esdf_cap = 0;        // voxels the ESDF workspace was laid out for
   size_t surface_cap = 0;     // cells of the block grid the surface-point workspace was laid out for
   size_t surface_mesh_cap = 0;  // cells of the block grid the surface-mesh workspace was laid out for
+  size_t regions_cap = 0;     // voxels the region workspace was laid out for
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
   EngineDev* d_eng = nullptr;  // device copy of the engine record (device_types.h)
 
@@ -1987,3 +1992,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "resample.inc" // ratsdf_resample_blocks_device / ratsdf_fuse_map_transformed (include/ratsdf_resample.h)
 #include "coarsen.inc"  // ratsdf_coarsen_blocks_device / ratsdf_fuse_map_coarsened (include/ratsdf_coarsen.h)
 #include "surface_mesh.inc"  // ratsdf_surface_mesh[_device] (include/ratsdf_surface_mesh.h)
+#include "regions.inc"  // ratsdf_regions[_device] (include/ratsdf_regions.h)

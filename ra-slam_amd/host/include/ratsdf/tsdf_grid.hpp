@@ -53,6 +53,9 @@ struct Api {
   // include/ratsdf_surface_mesh.h: likewise optional (not in the CPU oracle)
   int (*surface_mesh)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_surface_mesh_params*,
                       ratsdf_surface_point**, size_t*, int32_t**, size_t*) = nullptr;
+  // include/ratsdf_regions.h: likewise optional (not in the CPU oracle)
+  int (*regions)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_regions_params*, int32_t*,
+                 ratsdf_region**, size_t*) = nullptr;
   // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
   int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
   int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
@@ -131,6 +134,12 @@ class TSDFGrid {
   // the status (also kept in last_status()); both vectors are empty unless it is RATSDF_OK.  No reference counterpart.
   int SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
                   std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
+  // connected regions of a box of voxels (include/ratsdf_regions.h): the voxels that params admits grouped by face
+  // adjacency inside the box; *labels (may be nullptr) receives dims[0] * dims[1] * dims[2] labels, *regions the table,
+  // ascending in root.  Returns the status (also kept in last_status()); both vectors are empty unless it is RATSDF_OK.
+  // No reference counterpart.
+  int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
+              std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);
   // map fusion (include/ratsdf_fuse.h): another grid's map (same device, voxel size and truncation; only read), n
   // blocks in ratsdf_import_blocks' layout, or a checkpoint file merged into this map with the weighted-average voxel
   // update.  stats may be nullptr.  Return the status (also kept in last_status()); no reference counterpart.

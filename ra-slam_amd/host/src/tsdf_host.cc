@@ -86,6 +86,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
   api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
+  api.regions = reinterpret_cast<decltype(api.regions)>(opt_sym("regions"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -314,6 +315,30 @@ int TSDFGrid::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const 
   }
   if (v) api_->free_buffer(v);
   if (t) api_->free_buffer(t);
+  return status_;
+}
+
+int TSDFGrid::Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
+                      std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
+  if (labels) labels->clear();
+  if (regions) regions->clear();
+  if (!engine_ || !regions) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  if (labels) {  // (a box beyond the header's limits gets a one-voxel placeholder: the library refuses it)
+    size_t n = 1;
+    for (int a = 0; dims && a < 3; ++a) n = dims[a] >= 1 && dims[a] <= 1024 && n ? n * (size_t)dims[a] : 0;
+    labels->resize(dims && n && n <= ((size_t)1 << 27) ? n : 1);
+  }
+  ratsdf_region* r = nullptr;
+  size_t nr = 0;
+  note(api_->regions ? api_->regions(engine_, origin, dims, &params, labels ? labels->data() : nullptr, &r, &nr)
+                     : RATSDF_ERR_NOT_IMPLEMENTED,
+       "Regions");
+  if (status_ == RATSDF_OK) {
+    if (r) regions->assign(r, r + nr);
+  } else if (labels) {
+    labels->clear();
+  }
+  if (r) api_->free_buffer(r);
   return status_;
 }
 
@@ -634,6 +659,12 @@ int TSDFSystem::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], cons
                             std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.SurfaceMesh(origin, dims, params, vertices, triangles);
+}
+
+int TSDFSystem::Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
+                        std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.Regions(origin, dims, params, labels, regions);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

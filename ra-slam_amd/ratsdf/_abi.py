@@ -125,6 +125,19 @@ class SurfaceMeshParams(C.Structure):
                 ("reserved1", C.c_uint32)]
 
 
+# include/ratsdf_regions.h (connected regions of a box): handled like ESDF_SYMBOLS
+REGIONS_SYMBOLS = ["regions", "regions_device"]
+# ratsdf_region (32 bytes)
+REGION_DTYPE = np.dtype([("root", "<i4"), ("voxels", "<i4"), ("frontier", "<i4"), ("faces", "<u4"),
+                         ("lo", "<i2", (3,)), ("hi", "<i2", (3,)), ("reserved", "<u4")])
+assert REGION_DTYPE.itemsize == 32
+
+
+class RegionsParams(C.Structure):
+    """ratsdf_regions_params"""
+    _fields_ = [("occupied_below", C.c_float), ("min_prob", C.c_float), ("states", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class _OwnedBuffer:
     """a result buffer handed over by the library (malloc'ed there): exposes it through the array interface and gives
     it back with ratsdf_free_buffer when the last array built on it is collected"""
@@ -274,6 +287,16 @@ class Library:
                 f.argtypes = box + {"surface_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
                                                      C.POINTER(C.c_size_t)],
                                     "surface_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in REGIONS_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(RegionsParams)]
+                f.argtypes = box + {"regions": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
+                                    "regions_device": [vp, vp, C.c_int64, vp]}[s]
             self.fn[s] = f
 
         for s in FUSE_SYMBOLS:
@@ -738,6 +761,43 @@ class Engine:
             return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])
         if hasattr(d_counts, "numpy"):       # a devmem.DeviceArray
             return tuple(int(v) for v in d_counts.numpy().view(np.int64).reshape(-1)[:2])
+        return None                          # a raw pointer: the caller reads it
+
+    def regions(self, origin, dims, states=1 << ESDF_STATE_FREE, occupied_below=0.0, min_prob=0.0, with_labels=True):
+        """connected regions of a box of voxels (ratsdf_regions, include/ratsdf_regions.h): the voxels whose
+        ESDF_STATE_* is admitted by the bit mask `states` and whose probability is not below min_prob, grouped by face
+        adjacency inside the box.  Returns (labels, table): labels is an int32 array of shape (dims[2], dims[1],
+        dims[0]), -1 for a non-member and otherwise the smallest box index x + X * (y + Y * z) of the voxel's region;
+        table is REGION_DTYPE records, one per region, ascending in root (size, voxels that border UNKNOWN ones, box
+        faces reached, bounding box in absolute voxel indices).  Without with_labels only the table."""
+        o, d = _box3(origin, "origin"), _box3(dims, "dims")
+        n = int(np.prod([int(v) for v in d], dtype=object))
+        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
+        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+        labels = np.empty(shape, dtype=np.int32) if with_labels else None
+        params = RegionsParams(float(occupied_below), float(min_prob), int(states), 0)
+        p, m = C.c_void_p(), C.c_size_t()
+        _check(self.lib.fn["regions"](self._h, o, d, C.byref(params), labels.ctypes.data if with_labels else None,
+                                      C.byref(p), C.byref(m)), "regions")
+        table = self._take(p, m.value, REGION_DTYPE)
+        return (labels, table) if with_labels else table
+
+    def regions_device(self, origin, dims, d_labels, d_regions, capacity, d_count, states=1 << ESDF_STATE_FREE,
+                       occupied_below=0.0, min_prob=0.0):
+        """regions() into DEVICE buffers, asynchronous on the engine's stream: the labels to d_labels (dims[0] * dims[1]
+        * dims[2] int32, 16-byte aligned, or 0 for none), the first min(total, capacity) 32-byte records to d_regions
+        (16-byte aligned; 0 with capacity 0 for a pure count) and the total as an int64 to d_count.  Each buffer: a
+        torch tensor, a devmem.DeviceArray or a raw pointer.  Returns the total (this waits for the stream)."""
+        params = RegionsParams(float(occupied_below), float(min_prob), int(states), 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_labels, d_regions, d_count)]
+        _check(self.lib.fn["regions_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                             ptr[0] or None, ptr[1] or None, int(capacity), ptr[2] or None),
+               "regions_device")
+        self.synchronize()
+        if hasattr(d_count, "cpu"):          # a torch tensor
+            return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
+        if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
+            return int(d_count.numpy().view(np.int64).reshape(-1)[0])
         return None                          # a raw pointer: the caller reads it
 
     def gather_valid_mesh(self):
