@@ -30,6 +30,7 @@ extern "C" {
 #define RATSDF_DEFAULT_BLOCK_BITS 18  /* utils/tsdf/voxel_mem.cuh:11-13  NUM_BLOCK = 2^18     */
 #define RATSDF_DEFAULT_BUCKET_BITS 21 /* utils/tsdf/voxel_hash.cuh:13-15 NUM_BUCKET = 2^21    */
 #define RATSDF_ENTRIES_PER_BUCKET 2   /* utils/tsdf/voxel_hash.cuh:18-20                      */
+#define RATSDF_MAX_SHARD_SLAB_BITS 31 /* x >> shard_slab_bits is a shift of a 32-bit int      */
 
 typedef enum ratsdf_status {
   RATSDF_OK = 0,
@@ -109,7 +110,8 @@ typedef struct ratsdf_config {
   int32_t bucket_bits;  /* 0 -> RATSDF_DEFAULT_BUCKET_BITS */
   /* Block-ownership sharding across GPUs (no reference counterpart): a candidate block
    * is inserted only if owner(block) == shard_rank, owner = floormod(x >> shard_slab_bits, count).
-   * shard_count <= 1 disables the filter.  shard_slab_bits <= 0 -> 2 (slabs of four blocks), as block_bits 0. */
+   * shard_count <= 1 disables the filter.  shard_slab_bits <= 0 -> 2 (slabs of four blocks), as block_bits 0;
+   * above RATSDF_MAX_SHARD_SLAB_BITS it is refused.  So an engine holds 1 .. RATSDF_MAX_SHARD_SLAB_BITS. */
   int32_t shard_rank;
   int32_t shard_count;
   int32_t shard_slab_bits;

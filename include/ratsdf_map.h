@@ -28,6 +28,28 @@
  *            little-endian uint64 (the last one zero-padded to 8 bytes); h = 0xcbf29ce484222325, then for each
  *            word w: h = (h ^ w) * 0x100000001b3 (mod 2^64)
  *
+ * The directory rule.  The kernels that read a loaded directory check nothing, so a file is refused unless its
+ * entries are a hash table that lookups can walk.  An entry that is not stored reads as {offset 0, idx -1}; an entry
+ * is live if idx >= 0; mask = 2^(bucket_bits+1) - 1; hash(p) = (x * 73856093 ^ y * 19349669 ^ z * 83492791) mod
+ * 2^bucket_bits in uint32 arithmetic; an offset is sign-extended, added to the entry index modulo 2^32 and masked.
+ * lookup(p): e0 = 2 * hash(p); e0 if it is live with position p; else e0 + 1 if it is; else last = e0 + 1 and, while
+ * offset(last) != 0, last = (last + offset(last)) & mask, which is the answer if it is live with position p; else
+ * p is absent.
+ *   D1  walks end: following the offsets from any stored entry reaches an entry with offset 0 within n_entries steps
+ *       (no cycle, whether live or dead nodes form it, through the table's end or by an offset that is a multiple of
+ *       the table's size)
+ *   D2  a block is where lookups find it: lookup(position(e)) == e for every live entry e (no block in a wrong
+ *       bucket, none behind a cut link, no position held twice)
+ *   D3  no block behind a dead node: every entry whose offset lookup(position(e)) follows on its way to a live
+ *       entry e is live.  An allocation fills an empty home entry with offset 0 (voxel_hash.cu:67-78), which would
+ *       cut the chain at a dead node and lose the blocks behind it; Delete unlinks a node (voxel_hash.cu:135-187),
+ *       so no engine writes such a file
+ *   H   the header names a configuration ratsdf_create_ex accepts: voxel_size and truncation finite and > 0;
+ *       shard_count >= 1; with shard_count > 1, 0 <= shard_rank < shard_count; 1 <= shard_slab_bits <=
+ *       RATSDF_MAX_SHARD_SLAB_BITS (31: an engine never holds less, ratsdf_create_ex reads <= 0 as 2)
+ * A dead chain node with no block behind it is accepted (D1 holds for it as for any stored entry).  Which shard owns
+ * a position is not checked: blocks of other shards come in through ratsdf_import_blocks too.
+ *
  * Every call returns a ratsdf_status: an I/O failure, or a malformed, corrupted or mismatched file, is
  * RATSDF_ERR_BAD_ARGUMENT.
  */
@@ -45,10 +67,10 @@ extern "C" {
  * Refuses with the sticky status if one is set (ratsdf_recover first), and with RATSDF_ERR_DEVICE if the directory
  * names a pool block twice (such a map cannot be resumed; nothing is written).  The map is not changed. */
 int ratsdf_save_map(ratsdf_engine* e, const char* path);
-/* Validates the whole file on the host first; its voxel size, truncation, table bits and shard fields must equal
- * the engine's.  Then replaces the engine's map with the file's (no engine buffer is reallocated: captured batch
- * graphs and groups stay valid), clears a sticky error and tells a consumer of directory deltas to take a whole
- * directory next.  On refusal the map is unchanged. */
+/* Validates the whole file on the host first, the directory rule above included; its voxel size, truncation, table
+ * bits and shard fields must equal the engine's.  Then replaces the engine's map with the file's (no engine buffer
+ * is reallocated: captured batch graphs and groups stay valid), clears a sticky error and tells a consumer of
+ * directory deltas to take a whole directory next.  On refusal the map is unchanged. */
 int ratsdf_load_map(ratsdf_engine* e, const char* path);
 /* Host only -- no device, no engine: validates the whole file, fills cfg's voxel_size, truncation, block_bits,
  * bucket_bits and shard_* (the other fields are zeroed) and *n_blocks (live blocks).  Either pointer may be NULL. */

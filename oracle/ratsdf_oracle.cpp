@@ -862,12 +862,15 @@ extern "C" {
 
 int ratsdf_oracle_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   if (!cfg || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  if (!(cfg->voxel_size > 0) || !(cfg->truncation > 0)) return RATSDF_ERR_BAD_ARGUMENT;
+  if (!(cfg->voxel_size > 0) || !(cfg->truncation > 0) || !std::isfinite(cfg->voxel_size) ||
+      !std::isfinite(cfg->truncation))
+    return RATSDF_ERR_BAD_ARGUMENT;
   const int bb = cfg->block_bits ? cfg->block_bits : RATSDF_DEFAULT_BLOCK_BITS;
   const int kb = cfg->bucket_bits ? cfg->bucket_bits : RATSDF_DEFAULT_BUCKET_BITS;
   if (bb < 1 || bb > 22 || kb < 2 || kb > 26) return RATSDF_ERR_BAD_ARGUMENT;
   if (cfg->shard_count > 1 && (cfg->shard_rank < 0 || cfg->shard_rank >= cfg->shard_count))
     return RATSDF_ERR_BAD_ARGUMENT;
+  if (cfg->shard_slab_bits > RATSDF_MAX_SHARD_SLAB_BITS) return RATSDF_ERR_BAD_ARGUMENT;
   ratsdf_engine* e = new ratsdf_engine();
   e->vs = cfg->voxel_size;
   e->trunc = cfg->truncation;

@@ -11,6 +11,7 @@
 #include <sys/stat.h>
 
 #include <string>
+#include <unordered_map>
 
 #include "../../include/ratsdf_map.h"
 
@@ -183,8 +184,84 @@ struct MapContents {
 
 static bool read_all(FILE* f, void* dst, size_t n) { return n == 0 || fread(dst, 1, n, f) == n; }
 
-// Opens and validates the WHOLE file (header, sections against it, entries, heap, checksum) on the host.  `want`, if
-// given, is the engine's configuration: a file of another one is refused before its sections are read.
+// Rule H of ratsdf_map.h: the header's configuration is one an engine can have (ratsdf_create_ex)
+static bool map_header_ok(const MapHeader& h) {
+  if (!std::isfinite(h.voxel_size) || !(h.voxel_size > 0) || !std::isfinite(h.truncation) || !(h.truncation > 0))
+    return false;
+  if (h.shard_count < 1 || (h.shard_count > 1 && (h.shard_rank < 0 || h.shard_rank >= h.shard_count))) return false;
+  return h.shard_slab_bits >= 1 && h.shard_slab_bits <= RATSDF_MAX_SHARD_SLAB_BITS;
+}
+
+// Rules D1, D2 and D3 of ratsdf_map.h: the stored entries (ascending, in range -- checked by the caller) are a hash
+// table the kernels' lookups can walk.  An entry that is not stored reads as {offset 0, idx -1}.  The device code
+// checks nothing of this: find_block, alloc_request, block_present_pre and resolve_block follow offsets until one
+// is 0.
+static bool map_directory_ok(const std::vector<MapEntry>& ent, int bucket_bits) {
+  const uint32_t n = (uint32_t)ent.size();
+  const uint32_t entry_mask = (2u << bucket_bits) - 1u, bucket_mask = (1u << bucket_bits) - 1u;
+  std::unordered_map<uint32_t, uint32_t> record_of;  // entry index -> its record
+  record_of.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) record_of.emplace(ent[i].entry, i);
+  auto next = [&](uint32_t i) -> uint32_t {  // the record that record i's offset leads to; n: an entry not stored
+    const auto it = record_of.find((ent[i].entry + (uint32_t)(int32_t)ent[i].e.offset) & entry_mask);
+    return it == record_of.end() ? n : it->second;
+  };
+  // D1: the walk from every stored entry reaches offset 0.  Each record is stepped over once: a walk stops at a
+  // record an earlier walk has shown to end, and one that meets a record of its own path has found a cycle.
+  enum : uint8_t { kNotWalked = 0, kOnPath = 1, kEnds = 2 };
+  std::vector<uint8_t> state(n, kNotWalked);
+  std::vector<uint32_t> path;
+  for (uint32_t i = 0; i < n; ++i) {
+    path.clear();
+    uint32_t j = i;
+    while (j != n && state[j] == kNotWalked) {
+      state[j] = kOnPath;
+      path.push_back(j);
+      j = ent[j].e.offset ? next(j) : n;
+    }
+    if (j != n && state[j] == kOnPath) return false;
+    for (uint32_t k : path) state[k] = kEnds;
+  }
+  // D2 and D3: lookup(position(e)) == e for every live entry e, over live entries only.  A lookup of a position of
+  // bucket b reads entry 2b, entry 2b + 1 and the chain behind 2b + 1, and takes the first live entry with that
+  // position: every bucket with a stored home entry is walked once, the first entry of each of ITS positions is
+  // marked, and no live entry may stay unmarked.
+  struct Seen {
+    uint64_t pos;
+    uint32_t order, rec;
+  };
+  std::vector<uint8_t> found(n, 0);
+  std::vector<Seen> seen;
+  for (uint32_t i = 0; i < n;) {
+    const uint32_t b = ent[i].entry >> 1;
+    seen.clear();
+    auto visit = [&](uint32_t r) {
+      const Entry& e = ent[r].e;
+      if (e.idx >= 0 && block_hash(e.x, e.y, e.z, bucket_mask) == b)
+        seen.push_back(Seen{(uint64_t)(uint16_t)e.x | (uint64_t)(uint16_t)e.y << 16 | (uint64_t)(uint16_t)e.z << 32,
+                            (uint32_t)seen.size(), r});
+    };
+    if (!(ent[i].entry & 1u)) visit(i++);
+    if (i < n && ent[i].entry == 2u * b + 1u) {  // the list head
+      uint32_t j = i++;
+      visit(j);
+      // D3: the walk goes on over a dead node, but a block behind one is not marked
+      for (bool dead = ent[j].e.idx < 0; ent[j].e.offset && (j = next(j)) != n; dead = dead || ent[j].e.idx < 0)
+        if (!dead) visit(j);
+    }
+    std::sort(seen.begin(), seen.end(),
+              [](const Seen& x, const Seen& y) { return x.pos != y.pos ? x.pos < y.pos : x.order < y.order; });
+    for (size_t k = 0; k < seen.size(); ++k)
+      if (k == 0 || seen[k].pos != seen[k - 1].pos) found[seen[k].rec] = 1;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (ent[i].e.idx >= 0 && !found[i]) return false;
+  return true;
+}
+
+// Opens and validates the WHOLE file (header, sections against it, entries, heap, the directory rule, checksum) on
+// the host.  `want`, if given, is the engine's configuration: a file of another one is refused before its sections
+// are read.
 static int map_read_validate(const char* path, const MapHeader* want, MapContents* out, FILE** keep_open) {
   if (!path) return RATSDF_ERR_BAD_ARGUMENT;
   FILE* f = fopen(path, "rb");
@@ -248,6 +325,8 @@ static int map_read_validate(const char* path, const MapHeader* want, MapContent
     used[(size_t)v] = 2;
   }
   out->pool_idx.insert(out->pool_idx.end(), out->heap.begin() + h.free_low, out->heap.end());
+  // the header names a configuration an engine can have, and the entries are a directory that lookups can walk
+  if (!map_header_ok(h) || !map_directory_ok(out->entries, h.bucket_bits)) return RATSDF_ERR_BAD_ARGUMENT;
   // voxels: hashed in passing (the load reads them again from here, after the checksum has been checked)
   {
     std::vector<uint8_t> buf((size_t)kMapChunk * kMapRecordBytes);

@@ -1359,12 +1359,15 @@ extern "C" {
 
 int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   if (!cfg || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  if (!(cfg->voxel_size > 0) || !(cfg->truncation > 0)) return RATSDF_ERR_BAD_ARGUMENT;
+  if (!(cfg->voxel_size > 0) || !(cfg->truncation > 0) || !std::isfinite(cfg->voxel_size) ||
+      !std::isfinite(cfg->truncation))
+    return RATSDF_ERR_BAD_ARGUMENT;
   const int bb = cfg->block_bits ? cfg->block_bits : RATSDF_DEFAULT_BLOCK_BITS;
   const int kb = cfg->bucket_bits ? cfg->bucket_bits : RATSDF_DEFAULT_BUCKET_BITS;
   if (bb < 1 || bb > 24 || kb < 9 || kb > 26) return RATSDF_ERR_BAD_ARGUMENT;
   if (cfg->shard_count > 1 && (cfg->shard_rank < 0 || cfg->shard_rank >= cfg->shard_count))
     return RATSDF_ERR_BAD_ARGUMENT;
+  if (cfg->shard_slab_bits > RATSDF_MAX_SHARD_SLAB_BITS) return RATSDF_ERR_BAD_ARGUMENT;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RATSDF_ERR_NO_DEVICE;
   if (cfg->device < 0 || cfg->device >= ndev) return RATSDF_ERR_BAD_ARGUMENT;

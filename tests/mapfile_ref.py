@@ -79,7 +79,77 @@ def from_dumps(engine, segm_live=1):
     return build(engine_config(engine), entry_index, blocks, heap, free_low, segm_live, tsdf, rgbw, prob, free_rgbw)
 
 
-def parse(data):
+MAX_SHARD_SLAB_BITS = 31  # RATSDF_MAX_SHARD_SLAB_BITS (include/ratsdf.h)
+
+
+def check_directory(m):
+    """The directory rule of include/ratsdf_map.h on a parse() dict: None, or the name of the first violation --
+    "H <field>" (the header names no configuration an engine can have), "D1" (a walk along the offsets does not end),
+    "D2" (a live entry is not what a lookup of its position finds) or "D3" (the lookup steps over a dead node to find
+    it).  Restated from the rule's text, one plain
+    lookup per live entry; the engine's check is organised differently."""
+    import math
+
+    from kat_cases import ref_hash
+    for f in ("voxel_size", "truncation"):
+        if not (math.isfinite(m[f]) and m[f] > 0):
+            return "H " + f
+    if m["shard_count"] < 1:
+        return "H shard_count"
+    if m["shard_count"] > 1 and not 0 <= m["shard_rank"] < m["shard_count"]:
+        return "H shard_rank"
+    if not 1 <= m["shard_slab_bits"] <= MAX_SHARD_SLAB_BITS:
+        return "H shard_slab_bits"
+    bits = m["bucket_bits"]
+    mask = (2 << bits) - 1
+    b = m["blocks"]
+    stored = {int(e): (int(b["x"][i]), int(b["y"][i]), int(b["z"][i]), int(b["offset"][i]), int(b["idx"][i]))
+              for i, e in enumerate(m["entry_index"])}
+    empty = (0, 0, 0, 0, -1)  # what an entry that is not stored reads as
+
+    def offset(e):
+        return stored.get(e, empty)[3]
+
+    def step(e):  # int16 offset, sign-extended, added modulo 2^32, masked
+        return ((e + (offset(e) & 0xFFFFFFFF)) & 0xFFFFFFFF) & mask
+
+    def holds(e, p):
+        x, y, z, _, idx = stored.get(e, empty)
+        return idx >= 0 and (x, y, z) == p
+
+    ends = set()  # D1, memoised: entries from which the walk is known to reach offset 0
+    for e in stored:
+        path, cur = [], e
+        while cur not in ends and offset(cur) != 0:
+            if len(path) >= len(stored):
+                return "D1"
+            path.append(cur)
+            cur = step(cur)
+        ends.update(path)
+
+    def lookup(p):
+        e0 = 2 * ref_hash(p, bits)
+        if holds(e0, p):
+            return e0
+        if holds(e0 + 1, p):
+            return e0 + 1
+        last, over_dead = e0 + 1, False
+        while offset(last) != 0:
+            over_dead = over_dead or stored[last][4] < 0
+            last = step(last)
+            if holds(last, p):
+                return "behind a dead node" if over_dead else last
+        return None
+
+    found = {e: lookup((x, y, z)) for e, (x, y, z, _, idx) in stored.items() if idx >= 0}
+    if any(got != e and got != "behind a dead node" for e, got in found.items()):
+        return "D2"
+    if any(got != e for e, got in found.items()):
+        return "D3"
+    return None
+
+
+def parse(data, verify_checksum=True):
     """a map file's bytes -> dict of its header fields and sections (checks sizes and the checksum)"""
     data = bytes(data)
     (magic, version, hsize, vs, tr, bb, kb, srank, scount, sslab, segm_live, num_free, free_low, n_entries,
@@ -95,7 +165,7 @@ def parse(data):
     free = np.frombuffer(data, dtype=RGBW_DTYPE, count=(num_free - free_low) * 512, offset=off).reshape(-1, 512)
     off += free.nbytes
     assert len(data) == off + 8, "file size does not match the header"
-    assert struct.unpack_from("<Q", data, off)[0] == checksum(data[:off]), "checksum"
+    assert not verify_checksum or struct.unpack_from("<Q", data, off)[0] == checksum(data[:off]), "checksum"
     blocks = np.zeros(n_entries, dtype=BLOCK_DTYPE)
     for f in ("x", "y", "z", "offset", "idx"):
         blocks[f] = ent[f]
