@@ -339,7 +339,11 @@ int ratsdf_export_directory_delta_device(ratsdf_engine* e, void* d_payload, int3
  * NEIGHBOUR blocks (marching cubes: voxel_tsdf.cu:582-620 reads the 2x2x2 block neighbourhood) find them.
  * ratsdf_gather_valid_mesh of a sharded engine emits the cells of the blocks the engine OWNS only, so imported
  * blocks are read, never meshed.  Meant for a scratch engine built for one export (ratsdf.multi.mesh_across_shards);
- * frames integrated afterwards would update imported blocks like any other.  No reference counterpart. */
+ * frames integrated afterwards would update imported blocks like any other: whatever words they hold (any weight up
+ * to 255, tsdf of any size, +-inf or NaN, probabilities outside (0, 1)), a frame leaves what the reference's expressions
+ * (voxel_tsdf.cu:226-248) evaluate to in IEEE fp32 -- NaN and +-inf in the voxels where they do, the weight
+ * min(round(weight + w_new), 40) from the first update on, a voxel it does not update untouched bit for bit
+ * (tests/update_cases.py).  No reference counterpart. */
 int ratsdf_import_blocks(ratsdf_engine* e, int32_t n, const int16_t* block_pos, const float* tsdf,
                          const ratsdf_rgbw* rgbw, const float* prob);
 /* The same exchange with the voxel data staying in device memory (what the across-shard exports use under RCCL: the

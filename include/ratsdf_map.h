@@ -48,7 +48,9 @@
  *       shard_count >= 1; with shard_count > 1, 0 <= shard_rank < shard_count; 1 <= shard_slab_bits <=
  *       RATSDF_MAX_SHARD_SLAB_BITS (31: an engine never holds less, ratsdf_create_ex reads <= 0 as 2)
  * A dead chain node with no block behind it is accepted (D1 holds for it as for any stored entry).  Which shard owns
- * a position is not checked: blocks of other shards come in through ratsdf_import_blocks too.
+ * a position is not checked: blocks of other shards come in through ratsdf_import_blocks too.  Voxel words are not
+ * checked either: a frame onto a loaded map updates them as the reference's expressions evaluate in IEEE fp32, NaN and
+ * +-inf included, the weight capped at 40 by the first update (ratsdf_import_blocks in ratsdf.h).
  *
  * Every call returns a ratsdf_status: an I/O failure, or a malformed, corrupted or mismatched file, is
  * RATSDF_ERR_BAD_ARGUMENT.

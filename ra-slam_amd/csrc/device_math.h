@@ -83,8 +83,13 @@ __device__ inline int round_to_int(float x) {
 // v_div_fixup for operands near the ends of the exponent range and for inf / NaN / 0.  When several
 // numerators share one divisor the refined reciprocal r1 is computed once and every quotient costs
 // five instructions instead of ten -- the same FMA sequence, hence the same correctly rounded result,
-// for finite operands away from the exponent limits (|b| in [2^-60, 2^60], quotient not subnormal),
-// which is what the callers guarantee or guard.
+// for finite operands away from the exponent limits (|b| in [2^-60, 2^60], quotient not subnormal).
+// Without the fixup the sequence differs from IEEE `/` in three places: a numerator of +-inf gives NaN
+// (fma(-b, inf, inf)) where the quotient is that infinity, a numerator of -0 gives +0 (e2 = fma(-b, -0, -0)
+// = +0), and a subnormal quotient may be a subnormal step off.  NaN, overflow and underflow to zero come
+// out as in IEEE.  The pixel quotients guard the divisor (recip_safe) and have finite non-zero-or-harmless
+// numerators; the voxel update, whose numerator holds whatever tsdf word an imported map brought, mends
+// the first two with div_shared_fixup and leaves the third to the tolerance (tests/update_cases.py).
 struct Recip {
   float d, r1;
 };
@@ -100,9 +105,45 @@ __device__ inline float div_shared(float a, const Recip& b) {
   const float e3 = fmaf(-b.d, q1, a);
   return fmaf(e3, b.r1, q1);
 }
+// div_shared's `q` mended for a divisor >= 0 and any numerator: the quotient has the numerator's sign (OR-ing it in
+// only ever turns the +0 that came of a -0 into -0; a NaN stays a NaN), and an infinite numerator is its own quotient.
+// One v_cmp_class, one v_cndmask and the sign transfer per quotient, and no register beyond the two it is given.
+__device__ inline float div_shared_fixup(float a, float q) {
+  const float qs = __uint_as_float(__float_as_uint(q) | (__float_as_uint(a) & 0x80000000u));
+  return __builtin_amdgcn_class(a, 0x204) ? a : qs;  // -inf | +inf
+}
 __device__ inline bool recip_safe(float d) {  // divisor range in which div_shared equals IEEE `/`
   const float ad = fabsf(d);
   return ad > 1e-18f && ad < 1e18f;
+}
+
+// Natural log of the odds p / (1 - p) of a voxel's probability on the hardware's v_log_f32, which reads a subnormal
+// input as zero: a probability below FLT_MIN (only an imported map holds one) would come out as -inf instead of about
+// -90, and the update would turn it into NaN at weight 0 or against a pixel with lt = 0, where the reference's logf
+// gives a number.  Odds below FLT_MIN are therefore scaled by 2^32 before the logarithm and the 32 taken off after
+// it, as the compiler's own denormal-safe lowering of log2f does: a compare selects the exponent 32 there and 0
+// everywhere else (inline constants: a select between 2^32 and 1 wants a register the kernel does not have), v_ldexp
+// applies it, and the exponent comes off as a float.  ldexp(o, 0) and l - 0 are exact, so every other probability
+// gets the bits it always got.  Zero and negative odds take the scaled side and give -inf resp. NaN either way.
+__device__ inline float log_odds(float p) {
+  const float o = p * __builtin_amdgcn_rcpf(1.f - p);
+  const int e = o < 0x1p-126f ? 32 : 0;
+  return (__builtin_amdgcn_logf(__builtin_ldexpf(o, e)) - (float)e) * 0.69314718f;
+}
+
+// The word of the updated probability pn = 1 / (1 + exp(-x)).  For finite log-odds x below about -88 the exponential
+// overflows and pn comes out as 0, where the reference keeps a tiny number: harmless by itself (the tolerance is 1e-4)
+// but not for the next frame, which turns an exact 0 against a pixel with lt = 0 into NaN and a tiny number into 1.
+// So a finite x gives at least FLT_MIN; x = -inf (a prior of 0, a pixel with ht = 0) still gives the exact 0 and a
+// NaN stays one (unsigned maximum of the words: pn >= +0, and a NaN's word is above every number's).
+// This makes the frame after ONE overflowing step agree, no more: the reference's own pos = expf(...) underflows to an
+// exact 0 below about -104, which repeated frames with a tiny ht reach from a probability that is already tiny; the
+// next frame under lt = 0 is then NaN in the reference and 1 here.  No crafted pool of tests/update_cases.py goes
+// there, and no map built from ordinary ht / lt does.
+__device__ inline uint32_t probability_word(float x, float pn) {
+  const uint32_t w = __float_as_uint(pn);
+  const uint32_t floored = w > 0x00800000u ? w : 0x00800000u;
+  return x > -__builtin_inff() ? floored : w;
 }
 
 // Hash(), utils/tsdf/voxel_hash.cu:19-23

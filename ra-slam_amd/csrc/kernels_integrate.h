@@ -739,8 +739,11 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
       // one colour channel at a time, packed into the output words at once (short live ranges: the
       // kernel has 64 VGPRs).  roundf of a non-negative float = v_cvt_rpi_i32_f32 (floor(x + 0.5),
       // evaluated exactly by the hardware: equal to roundf for every non-negative float, checked
-      // exhaustively by tools/probes/round_probe.hip); quotients and the weight are non-negative and
-      // at most 255 / 44, never NaN (wc >= 1).
+      // exhaustively by tools/probes/round_probe.hip).  Quotients and the weight are non-negative: at most 255
+      // resp. 259 (an imported voxel's weight may be anything up to 255).  wc = 0 happens -- an imported voxel of
+      // weight 0 under a pixel at max_depth: the quotients are then 0 / 0 = NaN, which the conversion turns into
+      // INT_MIN, so the first channel is masked to its byte (the shifts drop the bit from the other two, and the
+      // weight converts to 0): colour 0, weight 0, as the reference's casts give.
       auto rpi = [](float x) {
         int r;
         asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
@@ -751,8 +754,8 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
         const v2f r_old = {(float)(c0 & 0xFFu), (float)(c1 & 0xFFu)};
         const v2f r_new = {(float)(n0 & 0xFFu), (float)(n1 & 0xFFu)};
         const v2f q = div2(r_old * wo + r_new * wn, wc, r1);                       // :234-235
-        o0 = rpi(q[0]);                                                            // :239-240
-        o1 = rpi(q[1]);
+        o0 = rpi(q[0]) & 0xFFu;                                                    // :239-240
+        o1 = rpi(q[1]) & 0xFFu;
       }
       {
         const v2f g_old = {(float)((c0 >> 8) & 0xFFu), (float)((c1 >> 8) & 0xFFu)};
@@ -774,7 +777,10 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
         o1 |= (w1 < 40u ? w1 : 40u) << 24;
       }
       const v2f t_old = {__uint_as_float(tv[0]), __uint_as_float(tv[1])};
-      const v2f t_new = div2(t_old * wo + ts * wn, wc, r1);                        // :236
+      const v2f t_num = t_old * wo + ts * wn;
+      v2f t_new = div2(t_num, wc, r1);                                             // :236
+#pragma unroll
+      for (int j = 0; j < 2; ++j) t_new[j] = div_shared_fixup(t_num[j], t_new[j]);
       const uint32_t ow[2] = {o0, o1};
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -785,11 +791,10 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
         // an unloaded register is dropped -- a uniform branch around these twelve instructions cost the kernel two
         // vector registers it does not have, i.e. scratch)
         const float pr = __uint_as_float(sv[j]);
-        const float odds = pr * __builtin_amdgcn_rcpf(1.f - pr);
-        const float L = __builtin_amdgcn_logf(odds) * 0.69314718f;
+        const float L = log_odds(pr);
         const float x = (wo[j] * L + wn[j] * ta[j].z) * r1[j];
         const float ex = __builtin_amdgcn_exp2f(x * -1.44269504f);
-        sv[j] = __float_as_uint(__builtin_amdgcn_rcpf(1.f + ex));
+        sv[j] = probability_word(x, __builtin_amdgcn_rcpf(1.f + ex));
       }
     }
     nupd = upd[0] || upd[1];  // (non-zero = something to store)
@@ -812,15 +817,18 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
       const uint32_t cn = tb[j];
       const float r_new = (float)(cn & 0xFFu), g_new = (float)((cn >> 8) & 0xFFu),
                   b_new = (float)((cn >> 16) & 0xFFu);
-      // wc = weight (1..40) + w_new (0..4): the quotients of :234-240 share it.  Numerators are
-      // bounded (bytes times weights, |tsdf| <= 1), so no operand leaves the range in which the
-      // shared-divisor form is the correctly rounded quotient; NaN propagates as in IEEE division.
+      // wc = weight (0..255: imported voxels) + w_new (0..4): the quotients of :234-240 share it.  It is 0 or lies
+      // in [2^-22, 259], so make_recip is exact about it (0: r1 = NaN, every quotient NaN = 0 / 0).  The colour
+      // numerators are finite and non-negative; the tsdf numerator holds whatever word the map brought -- it may
+      // be +-inf (a prior of +-inf, or one that overflows times its weight) or -0, where the shared-divisor form is
+      // not the IEEE quotient: div_shared_fixup (device_math.h).  NaN propagates as in IEEE division.
       const Recip rwc = make_recip(wc);
       const float rc = div_shared(r_old * wo + r_new * wn, rwc);        // :234-235
       const float gc = div_shared(g_old * wo + g_new * wn, rwc);
       const float bc = div_shared(b_old * wo + b_new * wn, rwc);
       const float t_old = __uint_as_float(tv[j]);
-      tv[j] = __float_as_uint(div_shared(t_old * wo + ts * wn, rwc));   // :236
+      const float t_num = t_old * wo + ts * wn;
+      tv[j] = __float_as_uint(div_shared_fixup(t_num, div_shared(t_num, rwc)));  // :236
       // quotients and the weight are non-negative: roundf without the sign step, and the byte pack
       // of an integer-valued float is exact in any rounding mode
       uint32_t o = 0;
@@ -837,11 +845,10 @@ __device__ inline void integrate_block(const Pool& pool, const FrameParams& P, c
         // tolerance on the probability is 1e-4, and it feeds nothing else).  0, 1, inf and NaN
         // behave as in the reference's form (ht = 0 -> p' = 0; ht = lt = 0 -> NaN; ...).
         const float pr = __uint_as_float(sv[j]);
-        const float odds = pr * __builtin_amdgcn_rcpf(1.f - pr);
-        const float L = __builtin_amdgcn_logf(odds) * 0.69314718f;
+        const float L = log_odds(pr);
         const float x = (wo * L + wn * ta[j].z) * rwc.r1;
         const float e = __builtin_amdgcn_exp2f(x * -1.44269504f);
-        sv[j] = __float_as_uint(__builtin_amdgcn_rcpf(1.f + e));
+        sv[j] = probability_word(x, __builtin_amdgcn_rcpf(1.f + e));
       }
       ++nupd;
     }

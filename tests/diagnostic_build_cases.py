@@ -157,3 +157,12 @@ def test_group_with_the_serial_role_at_the_tail_of_k_front(monkeypatch, make_eng
         c = engines[s].pipeline_counters()
         assert sum(c.values()) == n and (c["front_tail"] >= n - 1 if front_tail == "1" else c["front_tail"] == 0), c
     group.close()
+
+
+def test_crafted_prior_voxels_at_one_voxel_per_lane(monkeypatch, make_engine, make_oracle):
+    """RATSDF_VPL=1, the scalar loop the packed path is written against: the weight and tsdf pools of
+    tests/update_cases.py (crafted prior voxels; the carve blocks are part of every case) frame by frame, with the
+    assertions of tests/test_gpu_update_cases.py"""
+    from test_gpu_update_cases import one_voxel_per_lane
+    monkeypatch.setenv("RATSDF_VPL", "1")
+    one_voxel_per_lane(make_engine, make_oracle)
