@@ -24,14 +24,6 @@
 
 namespace ratsdf {
 
-// the box, and the block grid of its vertex owners: voxels [o, min(o + dims, 32767)] per axis
-struct MeshBox {
-  int ox, oy, oz;        // voxel index of the minimum corner
-  int X, Y, Z;           // voxels per axis
-  int bx0, by0, bz0;     // the first block of the grid
-  int nbx, nby, nbz;     // blocks per axis
-};
-
 struct SurfaceMeshTables {
   McTables mc;
   uint8_t ntri[256];  // triangles per sign pattern
@@ -49,11 +41,12 @@ inline SurfaceMeshTables make_surface_mesh_tables() {
 
 constexpr int kMeshCodes = 729;  // 9^3: the voxels of a block and the first layer of its upper neighbours
 
+// b: the box, its block grid that of the vertex owners, voxels [o, min(o + dims, 32767)] per axis (surface_mesh_box);
 // cnt_v / cnt_t: vertices / triangles per cell, code: 512 halfwords per cell (written by the count pass, read by the
 // emit pass); pos_v / pos_t / total[2]: the scans' results; out_v: 2 uint4 per vertex, out_t: 3 words per triangle;
 // d_counts: the two totals as int64
 template <bool kEmit>
-__global__ __launch_bounds__(512) void k_surface_mesh(Table tab, Pool pool, MeshBox b, uint32_t min_weight, float vs,
+__global__ __launch_bounds__(512) void k_surface_mesh(Table tab, Pool pool, MapBox b, uint32_t min_weight, float vs,
                                                       const SurfaceMeshTables* __restrict__ mt,
                                                       uint32_t* __restrict__ cnt_v, uint32_t* __restrict__ cnt_t,
                                                       uint16_t* __restrict__ code, const uint32_t* __restrict__ pos_v,

@@ -67,16 +67,38 @@ __device__ inline Trilinear trilinear(const float (&t)[8], float fx, float fy, f
   return r;
 }
 
-// A box of voxels and the map blocks it meets (the ESDF, the surface points): its cells are those blocks, x fastest.
+// A box of voxels and a grid of map blocks over it, x fastest: the cells of the read-outs that take a box (the ESDF,
+// the surface points, the welded mesh, the regions).  The block grid is the caller's choice: map_box() sets the blocks
+// the box meets, the welded mesh widens it to the blocks of its vertex owners (surface_mesh_box).
 struct MapBox {
   int ox, oy, oz;     // voxel index of the minimum corner
   int X, Y, Z;        // voxels per axis
-  int bx0, by0, bz0;  // the first map block the box meets
-  int nbx, nby;       // map blocks per axis it meets (x, y)
+  int bx0, by0, bz0;  // the first map block of the grid
+  int nbx, nby, nbz;  // map blocks per axis
 };
 inline size_t box_cells(const MapBox& b) {  // (host) cells of the box's block grid: one workgroup each
-  const int nbz = ((b.oz + b.Z - 1) >> 3) - b.bz0 + 1;
-  return (size_t)b.nbx * (size_t)b.nby * (size_t)nbz;
+  return (size_t)b.nbx * (size_t)b.nby * (size_t)b.nbz;
+}
+
+// (host) the box of an entry point's origin and dims, *n its voxels; false (RATSDF_ERR_BAD_ARGUMENT) unless every voxel
+// lies in the int16 range, no axis has more than 1024 and the box no more than kBoxMaxVoxels
+constexpr size_t kBoxMaxVoxels = (size_t)1 << 27;
+inline bool map_box(const int32_t* origin, const int32_t* dims, MapBox* b, size_t* n) {
+  if (!origin || !dims) return false;
+  size_t m = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (dims[a] < 1 || dims[a] > 1024 || origin[a] < -32768 || (int64_t)origin[a] + dims[a] - 1 > 32767) return false;
+    m *= (size_t)dims[a];
+  }
+  if (m > kBoxMaxVoxels) return false;
+  b->ox = origin[0], b->oy = origin[1], b->oz = origin[2];
+  b->X = dims[0], b->Y = dims[1], b->Z = dims[2];
+  b->bx0 = origin[0] >> 3, b->by0 = origin[1] >> 3, b->bz0 = origin[2] >> 3;
+  b->nbx = ((origin[0] + dims[0] - 1) >> 3) - b->bx0 + 1;
+  b->nby = ((origin[1] + dims[1] - 1) >> 3) - b->by0 + 1;
+  b->nbz = ((origin[2] + dims[2] - 1) >> 3) - b->bz0 + 1;
+  *n = m;
+  return true;
 }
 
 }  // namespace ratsdf

@@ -197,7 +197,7 @@ int ratsdf_gather_valid_mesh(ratsdf_engine* e, float** vertices, size_t* n_verti
     e->d_mc = std::move(mc);
   }
   // one scratch allocation: verts | vprob | vmask | vpos | tids | tmask | tpos | tile sums | total
-  const size_t ntile_max = (nts > nvs ? nts : nvs) / kScanTile + 2;
+  const size_t ntile_max = scan_tiles((nts > nvs ? nts : nvs) + 1) + 1;
   const size_t bytes = nvs * 12 + nvs * 4 * 3 + nts * 12 + nts * 4 * 2 + ntile_max * 4 + 64;
   DevMem d;  // the scratch (the compacted mesh leaves through the staging pair)
   StreamDrain drain{e->stream};

@@ -29,6 +29,7 @@
 #include "kernels_resample.h"
 #include "kernels_coarsen.h"
 #include "hip_mem.h"
+#include "workspace.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
 #include "../../include/ratsdf_surface.h"
@@ -36,6 +37,7 @@
 #include "../../include/ratsdf_regions.h"
 
 static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
+static_assert(ratsdf::kWsScanTile == (size_t)ratsdf::kScanTile, "scan_tiles() counts the tiles of kernels_mesh.h's scan");
 
 using namespace ratsdf;
 
@@ -232,24 +234,29 @@ class HostCopyPool {
   bool stop_ = false;
 };
 
+// The workspace of a box read-out: grown and carved by ratsdf_engine::workspace, with a layout of workspace.h.
+struct Workspace {
+  DevMem mem;
+  size_t cap = 0;  // items (voxels, cells of the block grid) it was laid out for
+};
+
 // What the engine owns of device and page-locked host memory: every buffer has ONE owner (hip_mem.h), and free_all()
 // drops them all by assigning an empty EngineMem.  `fixed` owns what is allocated once, at creation, pix_mem / rank_mem
 // the image-sized buffers (ensure_image): the typed pointers in Table, Pool and the engine's fields are views of them
 // (those structures go to the kernels by value).  A buffer that grows on demand is its own owner; a capacity counted
-// in other units than bytes (pixels, voxels) is zero while its buffers are replaced, so a failed grow is retried.
+// in other units than bytes (pixels, voxels, a Workspace's items) is zero while its buffers are replaced, so a failed
+// grow is retried.
 struct EngineMem {
   std::vector<DevMem> fixed, pix_mem, rank_mem;
   HostMem h_err_page;  // (ratsdf_engine::h_err)
   DevMem d_out;        // results on their way to the caller's host memory, and the page-locked buffer they pass
   HostMem h_out;       // through: ONE pair for every host-result entry point (ratsdf_engine::staging / download)
-  DevMem d_esdf;       // ESDF workspace (ratsdf_esdf*): state | x pass | y pass | two stacks (ratsdf_engine::esdf_cap)
-  DevMem d_surface;    // surface-point workspace (ratsdf_surface_points*): counts | starts | tile sums | total
-                       // (ratsdf_engine::surface_cap)
-  DevMem d_surface_mesh;      // surface-mesh workspace (ratsdf_surface_mesh*): counts | starts | tile sums | totals |
-                              // vertex codes (ratsdf_engine::surface_mesh_cap)
+  // the workspaces of the box read-outs, one buffer each (calls of two read-outs queued back to back share nothing)
+  Workspace ws_esdf;          // ratsdf_esdf*: esdf_layout, per voxel
+  Workspace ws_surface;       // ratsdf_surface_points*: surface_layout, per cell of the block grid
+  Workspace ws_surface_mesh;  // ratsdf_surface_mesh*: surface_mesh_layout, per cell of the block grid
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
-  DevMem d_regions;    // region workspace (ratsdf_regions*): seed bytes | labels | ranks | tile sums | total
-                       // (ratsdf_engine::regions_cap)
+  Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
@@ -357,10 +364,8 @@ struct ratsdf_engine : EngineMem {
   ratsdf_frame_stats* d_stats = nullptr;
   int staging(size_t dev_bytes, size_t host_bytes);
   int download(void* dst, const void* d_src, size_t bytes);
-  size_t esdf_cap = 0;        // voxels the ESDF workspace was laid out for
-  size_t surface_cap = 0;     // cells of the block grid the surface-point workspace was laid out for
-  size_t surface_mesh_cap = 0;  // cells of the block grid the surface-mesh workspace was laid out for
-  size_t regions_cap = 0;     // voxels the region workspace was laid out for
+  template <class Work>
+  int workspace(Workspace& ws, size_t n, void (*layout)(WsCursor&, size_t, Work*), Work* w);
   uint32_t* h_err = nullptr;  // page-locked landing place of the sticky error word (sticky())
   EngineDev* d_eng = nullptr;  // device copy of the engine record (device_types.h)
 
@@ -797,6 +802,22 @@ int ratsdf_engine::download(void* dst, const void* d_src, size_t bytes) {
     memcpy((uint8_t*)dst + o, h_out.as<void>(), m);
   }
   if (!bytes) HIPCHK(hipStreamSynchronize(stream));
+  return RATSDF_OK;
+}
+
+// The workspace of a box read-out for n items, carved into *w.  Grow-only: the stream is drained before the buffer is
+// replaced (an earlier call may still be using the old one), and the layout is that of the number of items the buffer
+// was allocated for, not of this call's n.
+template <class Work>
+int ratsdf_engine::workspace(Workspace& ws, size_t n, void (*layout)(WsCursor&, size_t, Work*), Work* w) {
+  if (ws.cap < n) {
+    HIPCHK(hipStreamSynchronize(stream));
+    ws.cap = 0;
+    STCHK(ws.mem.alloc(ws_bytes(layout, n)));
+    ws.cap = n;
+  }
+  WsCursor c{ws.mem.as<uint8_t>()};
+  layout(c, ws.cap, w);
   return RATSDF_OK;
 }
 
@@ -1339,19 +1360,71 @@ static int sticky_raised(ratsdf_engine* e) {
   return *(volatile uint32_t*)e->h_err != 0u ? e->sticky() : RATSDF_OK;
 }
 
+// ... behind the settled carve pass: what every entry point of a box read-out does after ENTRY
+static int box_entry(ratsdf_engine* e) {
+  STCHK(e->settle());
+  return sticky_raised(e);
+}
+
+// The exclusive scan of kernels_mesh.h, queued on the engine's stream: pos[i] = cnt[0] + .. + cnt[i - 1] and *d_total
+// their sum, for n counts (device arrays); `tiles` holds scan_tiles(n) words and is dead afterwards.  pos == cnt scans
+// in place (a thread of k_mask_positions reads its four counts before it writes their positions).  Does not wait.
+static int scan_counts(ratsdf_engine* e, const uint32_t* cnt, size_t n, uint32_t* tiles, uint32_t* d_total,
+                       uint32_t* pos) {
+  const uint32_t ntiles = (uint32_t)scan_tiles(n);
+  hipLaunchKernelGGL(k_mask_tile_sums, dim3(ntiles), dim3(1024), 0, e->stream, cnt, n, tiles);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, tiles, ntiles, d_total);
+  hipLaunchKernelGGL(k_mask_positions, dim3(ntiles), dim3(1024), 0, e->stream, cnt, n, tiles, pos);
+  HIPCHK(hipGetLastError());
+  return RATSDF_OK;
+}
+
 // exclusive positions of the set items of a 0/1 mask (device arrays), and in *h_total their number; waits for the stream
 // (rebuild_derived's free list, the mesh gather of query.inc)
 static int mask_positions(ratsdf_engine* e, const uint32_t* mask, size_t n, uint32_t* pos,
                           uint32_t* scratch_tiles, uint32_t* d_total, uint32_t* h_total) {
-  const uint32_t ntiles = (uint32_t)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(k_mask_tile_sums, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, scratch_tiles, ntiles,
-                     d_total);
-  hipLaunchKernelGGL(k_mask_positions, dim3(ntiles), dim3(1024), 0, e->stream, mask, n, scratch_tiles,
-                     pos);
+  STCHK(scan_counts(e, mask, n, scratch_tiles, d_total, pos));
   HIPCHK(hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return RATSDF_OK;
+}
+
+// A counted result leaves through the staging pair into fresh malloc memory, which the caller of the entry point owns:
+// up to two parts, laid side by side in d_out in their order, the first at offset 0.
+struct HostPart {
+  size_t count, record;  // records the count pass found, and the bytes of one
+  void** out;            // the entry point's outputs: null and zero unless everything has arrived
+  size_t* n_out;
+};
+// `emit(d)` queues the pass that writes part i at d[i].  Nulls the outputs first; with every count zero that is all
+// (the status is sticky()).  An empty part beside a filled one still gets an allocation of its own.  A failed malloc is
+// RATSDF_ERR_DEVICE with nothing queued (the caller's read of the counts drained the stream); after any failure every
+// part has been freed.
+template <class Emit>
+static int hand_over(ratsdf_engine* e, const HostPart* parts, int nparts, Emit emit) {
+  size_t bytes[2] = {0, 0}, sum = 0;
+  for (int i = 0; i < nparts; ++i) {
+    *parts[i].out = nullptr, *parts[i].n_out = 0;
+    bytes[i] = parts[i].count * parts[i].record;
+    sum += bytes[i];
+  }
+  if (sum == 0) return e->sticky();
+  STCHK(e->staging(sum, kHostChunk));
+  void* host[2] = {nullptr, nullptr};
+  uint8_t* dev[2] = {e->d_out.as<uint8_t>(), e->d_out.as<uint8_t>() + bytes[0]};
+  int st = RATSDF_OK;
+  for (int i = 0; i < nparts; ++i)
+    if (!(host[i] = malloc(bytes[i] ? bytes[i] : 1))) st = RATSDF_ERR_DEVICE;
+  if (st == RATSDF_OK) st = emit(dev);
+  for (int i = 0; i < nparts && st == RATSDF_OK; ++i) st = e->download(host[i], dev[i], bytes[i]);
+  if (st == RATSDF_OK) st = e->sticky();
+  for (int i = 0; i < nparts; ++i) {
+    if (st != RATSDF_OK)
+      free(host[i]);
+    else
+      *parts[i].out = host[i], *parts[i].n_out = parts[i].count;
+  }
+  return st;
 }
 
 // ================================== C ABI =====================================================
@@ -1836,7 +1909,7 @@ static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   Table& t = e->tab;
   const uint32_t occ_words = (t.num_entry + 63) / 64;
   const size_t nb = (size_t)t.num_block;
-  const uint32_t ntiles = (uint32_t)((nb + kScanTile - 1) / kScanTile);
+  const uint32_t ntiles = (uint32_t)scan_tiles(nb);
   DevMem tmp;  // unused flags | positions | tile sums | total
   STCHK(tmp.alloc((2 * nb + ntiles + 2) * 4));
   uint32_t *unused = tmp.as<uint32_t>(), *pos = unused + nb, *tiles = pos + nb, *d_total = tiles + ntiles + 1;

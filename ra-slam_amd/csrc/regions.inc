@@ -8,43 +8,14 @@ static_assert(sizeof(ratsdf_region) == 32 && offsetof(ratsdf_region, lo) == 16 &
               "ratsdf_region layout");
 static_assert(sizeof(ratsdf_regions_params) == 16, "ratsdf_regions_params layout");
 
-// the workspace of a box of n voxels: seed bytes (n B) | labels (4n B) | root flags, then ranks in place (4n B) | the
-// scan's tile sums | the number of regions (a word) and the host entry point's int64 count, 16 bytes together.  Its
-// own buffer: a field of esdf.inc queued before or after shares nothing with it.
-struct RegionsWork {
-  uint8_t* st;
-  int32_t* lab;
-  uint32_t *rank, *tiles, *total;
-  long long* count;
-};
-static size_t regions_work_bytes(size_t n) {
-  return esdf_round(n) + 2 * esdf_round(4 * n) + esdf_round(4 * surface_tiles(n)) + 16;
-}
+// The workspace is EngineMem::ws_regions (RegionsWork, workspace.h), per voxel.  Its own buffer: a field of esdf.inc
+// queued before or after shares nothing with it.
 
 // argument checks of both entry points (RATSDF_ERR_BAD_ARGUMENT when false)
 static bool regions_box(const int32_t* origin, const int32_t* dims, const ratsdf_regions_params* p, MapBox* b,
                         size_t* n) {
-  return p && !std::isnan(p->min_prob) && p->states >= 1u && p->states <= 7u && p->flags == 0u &&
-         esdf_box(origin, dims, p->occupied_below, 0u, b, n);
-}
-
-// a workspace for n voxels (laid out for the number it was allocated for)
-static int regions_workspace(ratsdf_engine* e, size_t n, RegionsWork* w) {
-  if (e->regions_cap < n) {
-    HIPCHK(hipStreamSynchronize(e->stream));  // an earlier call may still be using the old one
-    e->regions_cap = 0;
-    STCHK(e->d_regions.alloc(regions_work_bytes(n)));
-    e->regions_cap = n;
-  }
-  const size_t cap = e->regions_cap;
-  uint8_t* p = e->d_regions.as<uint8_t>();
-  w->st = p;
-  w->lab = (int32_t*)(p += esdf_round(cap));
-  w->rank = (uint32_t*)(p += esdf_round(4 * cap));
-  w->tiles = (uint32_t*)(p += esdf_round(4 * cap));
-  w->total = (uint32_t*)(p += esdf_round(4 * surface_tiles(cap)));
-  w->count = (long long*)(p + 8);
-  return RATSDF_OK;
+  return p && !std::isnan(p->min_prob) && !std::isnan(p->occupied_below) && p->states >= 1u && p->states <= 7u &&
+         p->flags == 0u && map_box(origin, dims, b, n);
 }
 
 // seed, local pass, border merge, flatten and the scan of the root flags: labels in w.lab (and d_labels when it is
@@ -65,13 +36,8 @@ static int regions_label(ratsdf_engine* e, const MapBox& b, size_t n, const rats
   hipLaunchKernelGGL(k_regions_flatten, dim3(per_voxel), dim3(256), 0, e->stream, w.lab, (uint32_t)n, d_labels,
                      w.rank);
   HIPCHK(hipGetLastError());
-  const uint32_t ntiles = (uint32_t)surface_tiles(n);
-  hipLaunchKernelGGL(k_mask_tile_sums, dim3(ntiles), dim3(1024), 0, e->stream, w.rank, n, w.tiles);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, w.tiles, ntiles, w.total);
-  // (in place: a thread reads its four flags before it writes their positions)
-  hipLaunchKernelGGL(k_mask_positions, dim3(ntiles), dim3(1024), 0, e->stream, w.rank, n, w.tiles, w.rank);
-  HIPCHK(hipGetLastError());
-  return RATSDF_OK;
+  // (in place: a thread of the scan's last kernel reads its four flags before it writes their positions)
+  return scan_counts(e, w.rank, n, w.tiles, w.total, w.rank);
 }
 
 // the table: the first min(total, capacity) records at d_regions, the total as an int64 at d_count
@@ -102,10 +68,9 @@ int ratsdf_regions_device(ratsdf_engine* e, const int32_t origin[3], const int32
   ENTRY(e, capacity >= 0 && (d_regions || capacity == 0) && !((uintptr_t)d_regions & 15u) &&
                !((uintptr_t)d_labels & 15u) && d_count && !((uintptr_t)d_count & 7u) &&
                regions_box(origin, dims, params, &b, &n));
-  STCHK(e->settle());
-  STCHK(sticky_raised(e));
+  STCHK(box_entry(e));
   RegionsWork w;
-  STCHK(regions_workspace(e, n, &w));
+  STCHK(e->workspace(e->ws_regions, n, regions_layout, &w));
   STCHK(regions_label(e, b, n, *params, w, (int32_t*)d_labels));
   return regions_table(e, b, n, w, d_regions, capacity, d_count);
 }
@@ -115,32 +80,20 @@ int ratsdf_regions(ratsdf_engine* e, const int32_t origin[3], const int32_t dims
   MapBox b;
   size_t n = 0;
   ENTRY(e, out && n_out && regions_box(origin, dims, params, &b, &n));
-  STCHK(e->settle());
-  STCHK(sticky_raised(e));
+  STCHK(box_entry(e));
   RegionsWork w;
-  STCHK(regions_workspace(e, n, &w));
+  STCHK(e->workspace(e->ws_regions, n, regions_layout, &w));
   STCHK(e->staging(0, kHostChunk));
   STCHK(regions_label(e, b, n, *params, w, nullptr));
   uint32_t total = 0;
   STCHK(e->read_small(&total, w.total, 4));
-  *out = nullptr;
+  *out = nullptr;  // (before the labels: a failed download of theirs leaves no table either)
   *n_out = 0;
   if (labels) STCHK(e->download(labels, w.lab, n * sizeof(int32_t)));
-  if (total == 0u) return e->sticky();
-  const size_t bytes = (size_t)total * sizeof(ratsdf_region);
-  STCHK(e->staging(bytes, kHostChunk));
-  void* host = malloc(bytes);
-  if (!host) return RATSDF_ERR_DEVICE;  // (nothing is queued: read_small drained the stream)
-  int st = regions_table(e, b, n, w, e->d_out.as<void>(), (int64_t)total, w.count);
-  if (st == RATSDF_OK) st = e->download(host, e->d_out.as<void>(), bytes);
-  if (st == RATSDF_OK) st = e->sticky();
-  if (st != RATSDF_OK) {
-    free(host);
-    return st;
-  }
-  *out = (ratsdf_region*)host;
-  *n_out = total;
-  return RATSDF_OK;
+  const HostPart part = {total, sizeof(ratsdf_region), (void**)out, n_out};
+  return hand_over(e, &part, 1, [&](uint8_t* const* d) {
+    return regions_table(e, b, n, w, d[0], (int64_t)total, w.count);
+  });
 }
 
 }  // extern "C"

@@ -1,0 +1,111 @@
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc) carve their device
+// workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
+// struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
+// written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
+// compiles it alone.  ratsdf_engine::workspace (ratsdf_engine.hip) owns the buffers and their grow step.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace ratsdf {
+
+inline size_t ws_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+constexpr size_t kWsScanTile = 4096;  // kScanTile of kernels_mesh.h (ratsdf_engine.hip asserts it)
+inline size_t scan_tiles(size_t n) { return (n + kWsScanTile - 1) / kWsScanTile; }  // tile sums of a scan over n items
+
+struct WsCursor {
+  uint8_t* base;  // null: nothing is carved, only measured
+  size_t off = 0;
+  // the current position as a T*, then on by exactly `bytes` ...
+  template <class T>
+  T* take_raw(size_t bytes) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += bytes;
+    return p;
+  }
+  // ... or by ws_round(bytes): the next part starts 256-aligned again
+  template <class T>
+  T* take(size_t bytes) {
+    return take_raw<T>(ws_round(bytes));
+  }
+};
+
+// the bytes of a layout for n items
+template <class Work>
+size_t ws_bytes(void (*layout)(WsCursor&, size_t, Work*), size_t n) {
+  WsCursor c{nullptr};
+  Work w;
+  layout(c, n, &w);
+  return c.off;
+}
+
+// The layouts.  Offsets and sizes are, for every n, those of the hand-written sums and pointer chains they replace
+// (the test pins the sums): the alignment the kernels see and the memory footprint are unchanged.
+
+// ESDF, a box of n voxels: state (n B) | x pass (4n B; the host entry point's field after the z pass) | y pass (8n B) |
+// stack of the transform to O (8n B) | stack of the transform to box \ O (8n B); the 8-byte records are uint2
+struct EsdfWork {
+  uint8_t* st;
+  uint32_t* gx;
+  uint64_t *gy, *stk0, *stk1;
+};
+inline void esdf_layout(WsCursor& c, size_t n, EsdfWork* w) {  // (offsets and size as before, see above)
+  w->st = c.take<uint8_t>(n);
+  w->gx = c.take<uint32_t>(4 * n);
+  w->gy = c.take<uint64_t>(8 * n);
+  w->stk0 = c.take<uint64_t>(8 * n);
+  w->stk1 = c.take<uint64_t>(8 * n);
+}
+
+// surface points, a box of n cells of the block grid: points per cell (4n B) | where each cell's points start (4n B) |
+// the scan's tile sums | the total (a word) and the host entry point's int64 count, 16 bytes together
+struct SurfaceWork {
+  uint32_t *cnt, *pos, *tiles, *total;
+  long long* count;
+};
+inline void surface_layout(WsCursor& c, size_t n, SurfaceWork* w) {  // (offsets and size as before, see above)
+  w->cnt = c.take<uint32_t>(4 * n);
+  w->pos = c.take<uint32_t>(4 * n);
+  w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
+  w->total = c.take_raw<uint32_t>(8);
+  w->count = c.take_raw<long long>(8);
+}
+
+// welded mesh, a grid of n block cells: vertices per cell | triangles per cell | where each cell's vertices start |
+// where its triangles start (4n B each) | the scan's tile sums | the two totals (words) and the host entry point's two
+// int64 counts, a rounded 32 bytes together | the vertex codes, 512 halfwords per cell
+struct SurfaceMeshWork {
+  uint32_t *cnt_v, *cnt_t, *pos_v, *pos_t, *tiles, *total;
+  long long* counts;
+  uint16_t* code;
+};
+inline void surface_mesh_layout(WsCursor& c, size_t n, SurfaceMeshWork* w) {  // (offsets and size as before, see above)
+  w->cnt_v = c.take<uint32_t>(4 * n);
+  w->cnt_t = c.take<uint32_t>(4 * n);
+  w->pos_v = c.take<uint32_t>(4 * n);
+  w->pos_t = c.take<uint32_t>(4 * n);
+  w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
+  w->total = c.take_raw<uint32_t>(8);
+  w->counts = c.take_raw<long long>(ws_round(32) - 8);
+  w->code = c.take_raw<uint16_t>(1024 * n);
+}
+
+// regions, a box of n voxels: seed bytes (n B) | labels (4n B) | root flags, then ranks in place (4n B) | the scan's
+// tile sums | the number of regions (a word) and the host entry point's int64 count, 16 bytes together
+struct RegionsWork {
+  uint8_t* st;
+  int32_t* lab;
+  uint32_t *rank, *tiles, *total;
+  long long* count;
+};
+inline void regions_layout(WsCursor& c, size_t n, RegionsWork* w) {  // (offsets and size as before, see above)
+  w->st = c.take<uint8_t>(n);
+  w->lab = c.take<int32_t>(4 * n);
+  w->rank = c.take<uint32_t>(4 * n);
+  w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
+  w->total = c.take_raw<uint32_t>(8);
+  w->count = c.take_raw<long long>(8);
+}
+
+}  // namespace ratsdf

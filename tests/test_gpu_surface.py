@@ -232,6 +232,23 @@ def test_random_map(make_engine, random_map):
     _check(e, blocks, [-17, -9, -1], [34, 34, 34], min_weight=255, min_prob=0.9)
 
 
+def test_workspace_grows_then_a_small_box_again(make_engine, random_map):
+    # one engine, its workspace laid out for a few cells, then for 17^3 = 4913 (the scan takes two tiles of 4096), then
+    # used by boxes far smaller than what it was laid out for.  The map: the random blocks at z 0 .. 3 and a slab of
+    # eight at z 14, 15, whose cells of the large box lie beyond 4096 (x fastest: 289 per layer of z, the box starts
+    # at block z -1).
+    far = ref.solid((3, 2, 14), (4, 3, 15), _checker(12))
+    e, blocks = _engine(make_engine, tuple(np.concatenate([a, b]) for a, b in zip(random_map, far)))
+    assert len(blocks) <= 64
+    small = ([-13, -5, 3], [22, 27, 19])
+    first = _check(e, blocks, *small)
+    large = _check(e, blocks, [-64, -64, -8], [136, 136, 136])
+    in_far = large["pos"][:, 2] >= np.float32(14 * 8) * np.float32(VS)
+    assert len(first) > 100 and in_far.sum() > 1000 and (~in_far).sum() > 5000
+    assert len(_check(e, blocks, [24, 16, 112], [8, 8, 8])) >= 3 * 64 * 7    # one block of the slab
+    assert ref.same_bytes(_check(e, blocks, *small), first)
+
+
 # ---- 6. capacity -----------------------------------------------------------------------------------------------
 def test_capacity(make_engine, random_map):
     import torch
