@@ -165,8 +165,8 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
   // ---- launches ----
   const bool fused = e0->fused_serial && e0->vpl != 1;
   ratsdf_engine::Geom g1 = e0->geometry(height, width, true, e0->vpl == 1 ? 100 : g->split_a,
-                                        (fused || e0->vpl == 1) ? 0 : g->split_b);
-  ratsdf_engine::Geom g0 = e0->geometry(height, width, false, 0, 0);
+                                        (fused || e0->vpl == 1) ? 0 : g->split_b, !fused);
+  ratsdf_engine::Geom g0 = e0->geometry(height, width, false, 0, 0, false);
   // Several members at VGA-sized images: a member's slice of 1 536 update workgroups (two blocks each at 640x480 /
   // 5 mm) instead of 4 096 -- a quarter of those are idle and still have to be dispatched, slice after slice
   // (4 members, round 4: 46.3 k frames/s at 4 096, 47.1 k at 3 072, 48.0 k at 2 048, 48.9 k at 1 536 and 1 024;

@@ -30,6 +30,7 @@
 #include "kernels_coarsen.h"
 #include "hip_mem.h"
 #include "workspace.h"
+#include "cand_shares.h"
 #include "../../include/ratsdf_sample.h"
 #include "../../include/ratsdf_esdf.h"
 #include "../../include/ratsdf_surface.h"
@@ -536,7 +537,7 @@ struct ratsdf_engine : EngineMem {
     unsigned n_vis_wg, parts, n_front_wg, n_cand_wg, grid;
     AheadGeom a, b, c;  // look-ahead shares of k_front, k_alloc_rank, k_integrate
   };
-  Geom geometry(int H, int W, bool has_next, int split_a, int split_b) const;
+  Geom geometry(int H, int W, bool has_next, int split_a, int split_b, bool b_launched) const;
   int lookahead_split(size_t npix) const;
   bool graph_eligible(int n, int H, int W) const;
   // A slot of the staging ring (depth | ht | lt | rgb, 16 bytes per pixel of the ring's largest image): its
@@ -961,8 +962,9 @@ CandJob ratsdf_engine::cand_job(const FrameIn& in, const FrameParams& P, unsigne
 
 // Launch geometry of a frame: workgroup counts and the split of the NEXT frame's candidate pass over
 // this frame's three launches (percent in k_front and in k_alloc_rank; the rest rides in k_integrate).
-ratsdf_engine::Geom ratsdf_engine::geometry(int H, int W, bool has_next, int split_a,
-                                            int split_b) const {
+// `b_launched`: the frame has a k_alloc_rank launch -- a share without a launch gets no tiles.
+ratsdf_engine::Geom ratsdf_engine::geometry(int H, int W, bool has_next, int split_a, int split_b,
+                                            bool b_launched) const {
   Geom g;
   memset(&g, 0, sizeof(g));
   const size_t npix = (size_t)H * W;
@@ -973,20 +975,16 @@ ratsdf_engine::Geom ratsdf_engine::geometry(int H, int W, bool has_next, int spl
   g.a.tiles_x_magic = g.b.tiles_x_magic = g.c.tiles_x_magic = cand_tiles_magic(tiles_x);
   g.a.tiles_per_wg = g.b.tiles_per_wg = g.c.tiles_per_wg = 4;
   if (has_next) {
-    // k_front and k_integrate take whole 16x16 super-tiles (4 tiles per 256-thread workgroup)
-    // (shares begin at multiples of 16 super-tiles: cand_pixel_work pairs neighbouring super-tiles per XCD)
-    const uint32_t tiles_a = (uint32_t)((uint64_t)(tiles / 4) * (unsigned)split_a / 100) / 16 * 64;
-    uint32_t tiles_b = (uint32_t)((uint64_t)(tiles / 4) * (unsigned)split_b / 100) / 16 * 64;
-    if (split_a + split_b >= 100 || tiles_a + tiles_b > tiles) tiles_b = tiles - tiles_a;
-    g.a.n_tiles = tiles_a;
-    g.b.first_tile = tiles_a;
-    g.b.n_tiles = tiles_b;
-    // k_alloc_rank runs 1024-thread workgroups; a look-ahead workgroup uses as many of its 16 waves
-    // as it needs to cover its tiles
-    const uint32_t tpw = (tiles_b + cand_wgs - 1) / cand_wgs;
-    g.b.tiles_per_wg = std::min<uint32_t>(std::max<uint32_t>(tpw, 1u), 16u);
-    g.c.first_tile = tiles_a + tiles_b;
-    g.c.n_tiles = tiles - tiles_a - tiles_b;
+    // (the arithmetic and what the kernels rely on: cand_shares.h)
+    const CandShares sh = cand_shares(H, W, split_a, split_b, cand_wgs, b_launched);
+    auto set = [](AheadGeom& ag, const CandShare& s) {
+      ag.first_tile = s.first_tile;
+      ag.n_tiles = s.n_tiles;
+      ag.tiles_per_wg = s.tiles_per_wg;
+    };
+    set(g.a, sh.a);
+    set(g.b, sh.b);
+    set(g.c, sh.c);
   }
   // visible-list workgroups: one lane per pool slot, from the top of the pool down (kernels_visible.h); 128 of them
   // cover a map of 65 536 blocks in one round of two loads per lane, larger maps take more rounds
@@ -1047,8 +1045,9 @@ int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, 
 #else
   const bool inline_kernel = inline_cand;
 #endif
-  const int split_b = (fused_serial && vpl != 1) ? 0 : (int)(cand_split_env ? cand_split_b : 0u);
-  const Geom g = geometry(H, W, next != nullptr, lookahead_split(npix), split_b);
+  const bool fused = fused_serial && vpl != 1;
+  const int split_b = fused ? 0 : (int)(cand_split_env ? cand_split_b : 0u);
+  const Geom g = geometry(H, W, next != nullptr, lookahead_split(npix), split_b, !fused);
   // shares of the next frame's candidate pass: k_front, k_alloc_rank, k_integrate
   CandJob ahead_a, ahead_b, ahead_c;
   memset(&ahead_a, 0, sizeof(ahead_a));
@@ -1072,7 +1071,6 @@ int ratsdf_engine::frame(const FrameIn& cur, const FrameIn* next, int H, int W, 
   cand_ready = next != nullptr;
 
   // fr[par] was zeroed when the frame before last was finalised (or at creation)
-  const bool fused = fused_serial && vpl != 1;
   if (inline_kernel) {
     const CandJob now = cand_job(cur, P, par);
     const unsigned n_now_wg = (now.n_tiles + 3) / 4;
@@ -1340,8 +1338,8 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
         hipEventCreateWithFlags(&g.ev[i], hipEventDisableTiming) != hipSuccess)
       return fail("staging allocation");
   // (graph_eligible: the serial role rides in k_integrate_g, whose first 8 extra workgroups are its own)
-  const Geom g1 = geometry(H, W, true, lookahead_split((size_t)H * W), 0);
-  const Geom g0 = geometry(H, W, false, 0, 0);
+  const Geom g1 = geometry(H, W, true, lookahead_split((size_t)H * W), 0, false);
+  const Geom g0 = geometry(H, W, false, 0, 0, false);
   if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) return fail("hipStreamBeginCapture");
   const Enqueued q = enqueue_jobs(stream, (EnginePtr)d_eng, d_jobs, n, 1, g0, g1, commit_rotation(g0.grid, g0.grid), 8u,
                                   (tab.tail_on ? 1u : 0u) | front_prio, vpl, nullptr);

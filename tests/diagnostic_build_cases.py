@@ -166,3 +166,17 @@ def test_crafted_prior_voxels_at_one_voxel_per_lane(monkeypatch, make_engine, ma
     from test_gpu_update_cases import one_voxel_per_lane
     monkeypatch.setenv("RATSDF_VPL", "1")
     one_voxel_per_lane(make_engine, make_oracle)
+
+
+def test_crafted_candidate_frames_under_other_look_ahead_splits(monkeypatch, make_engine, make_oracle):
+    """the 250x157, 353x97 and 1000x600 batches of tests/cand_cases.py (the smallest image with a non-empty share A, a
+    partial last group of workgroups, a ragged super-tile count above the HD threshold) with the look-ahead pass cut
+    differently: none, half and all of it in k_front; 30 % each in k_front and in a k_alloc_rank that is really
+    launched (RATSDF_FUSED_SERIAL=0); one voxel per lane, where k_integrate hosts none of it"""
+    import cand_cases as cc
+    from test_gpu_cand_cases import as_a_batch
+    switches = [dict(RATSDF_CAND_SPLIT="0"), dict(RATSDF_CAND_SPLIT="50"), dict(RATSDF_CAND_SPLIT="100"),
+                dict(RATSDF_CAND_SPLIT="30,30", RATSDF_FUSED_SERIAL="0"), dict(RATSDF_VPL="1")]
+    for env in switches:
+        for size in ((250, 157), (353, 97), (1000, 600)):
+            as_a_batch(cc.ragged(*size), "0", monkeypatch, make_engine, make_oracle, env)
