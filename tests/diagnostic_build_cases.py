@@ -168,6 +168,17 @@ def test_crafted_prior_voxels_at_one_voxel_per_lane(monkeypatch, make_engine, ma
     one_voxel_per_lane(make_engine, make_oracle)
 
 
+@pytest.mark.parametrize("vpl", ["1", "4"])
+def test_crafted_poses_and_borders_in_the_scalar_loop(vpl, monkeypatch, make_engine, make_oracle):
+    """RATSDF_VPL=1 / 4: the halves, plane and far families of tests/proj_cases.py frame by frame through the scalar
+    projection loop (f2i(roundf()) instead of the packed path's short pixel pick; at four voxels per lane ONE guard
+    for the lane's four divisors, of which the plane family makes one zero), with the assertions of
+    tests/test_gpu_update_cases.py"""
+    from test_gpu_proj_cases import other_voxels_per_lane
+    monkeypatch.setenv("RATSDF_VPL", vpl)
+    other_voxels_per_lane(make_engine, make_oracle)
+
+
 def test_crafted_candidate_frames_under_other_look_ahead_splits(monkeypatch, make_engine, make_oracle):
     """the 250x157, 353x97 and 1000x600 batches of tests/cand_cases.py (the smallest image with a non-empty share A, a
     partial last group of workgroups, a ragged super-tile count above the HD threshold) with the look-ahead pass cut

@@ -41,10 +41,11 @@ def same_pools(gpu, cpu):
         return False
 
 
-def compare(gpu, cpu, what, alive, prior=None, fr=None):
+def compare(gpu, cpu, what, alive, prior=None, fr=None, predict=uc.predict):
     """the HIP engine's map against the oracle's at the bars of the module docstring; alive: keys of the imported blocks
     that never left the map (every colour byte of theirs is known); prior (the oracle's map before the frame) and fr:
-    the frame whose 0 / 1 probabilities are looked at.  Returns the figures."""
+    the frame whose 0 / 1 probabilities are looked at; predict: the restatement of the case module the frame comes from
+    (update_cases or proj_cases).  Returns the figures."""
     assert_pool_consistent(gpu)
     strict = same_pools(gpu, cpu)
     g, o = uc.by_position(dump_set(gpu)), uc.by_position(dump_set(cpu))
@@ -55,7 +56,7 @@ def compare(gpu, cpu, what, alive, prior=None, fr=None):
         if prior is None:
             return ""
         at, held = uc.align(prior, o)
-        pr = uc.predict(o[0], fr)
+        pr = predict(o[0], fr)
         out = []
         for b, v in np.argwhere(bad)[:6]:
             was = (f"held tsdf {prior[1][at[b], v]!r} rgbw {prior[2][at[b], v]} p {prior[3][at[b], v]!r}" if held[b]
@@ -99,7 +100,7 @@ def compare(gpu, cpu, what, alive, prior=None, fr=None):
     n01 = 0
     if prior is not None and fr.ht is not None:
         at, held = uc.align(prior, o)
-        pr = uc.predict(o[0][held], fr)
+        pr = predict(o[0][held], fr)
         p0 = prior[3][at[held]]
         h, l = fr.ht.reshape(-1)[pr.k], fr.lt.reshape(-1)[pr.k]
         sel = pr.upd & ((p0 == 0) | (p0 == 1) | (h == 0) | (h == 1) | (l == 0) | (l == 1))
@@ -122,27 +123,32 @@ def still_alive(alive, cpu):
     return alive[np.isin(alive, uc.keys(np.stack([blocks["x"], blocks["y"], blocks["z"]], axis=1)))]
 
 
-def frame_by_frame(gpu, cpu, cs, send, what):
-    """every frame of the case into both engines (`send` puts frame i into the HIP engine), compared after each"""
+def frame_by_frame(gpu, cpu, cs, send, what, mod=uc):
+    """every frame of the case into both engines (`send` puts frame i into the HIP engine), compared after each.
+    mod: the module the case comes from (update_cases, or proj_cases with its own restatement).  Returns the figures
+    of every frame."""
     alive = uc.keys(cs.blocks[0])
+    figures = []
     for i, fr in enumerate(cs.frames):
         before_g, before_o = dump_set(gpu), dump_set(cpu)
         send(i, fr)
         cpu.integrate(*fr.args())
         assert_stats_equal(gpu, cpu, STATS)
-        if i == 1:
+        if mod is uc and i == 1:
             assert gpu.last_frame_stats()["allocated_blocks"] > 0  # fresh and loaded blocks in one launch
         alive = still_alive(alive, cpu)
-        assert len(alive) >= 16
-        compare(gpu, cpu, f"{what} frame {i}", alive, before_o, fr)
-        uc.untouched_unchanged(before_g, dump_set(gpu), fr)
+        assert len(alive) >= (16 if mod is uc else 1)
+        figures.append(compare(gpu, cpu, f"{what} frame {i}", alive, before_o, fr, mod.predict))
+        uc.untouched_unchanged(before_g, dump_set(gpu), fr, mod.predict)
     assert gpu.totals() == cpu.totals()
+    return figures
 
 
 def upload(cs):
     import torch
     dev = torch.device("cuda", 0)
-    out = [{k: torch.from_numpy(np.array(a)).to(dev) for k, a in fr._asdict().items() if a is not None} for fr in cs.frames]
+    out = [{k: torch.from_numpy(np.array(getattr(fr, k))).to(dev) for k in ("rgb", "depth", "ht", "lt")
+            if getattr(fr, k) is not None} for fr in cs.frames]
     torch.cuda.synchronize()
     return out
 
@@ -180,25 +186,29 @@ def batch_of(engine_or_group, devs):
                                       [wrap(uc.POSE)] * 3)
 
 
-def after_the_batch(gpu, cpu, cs, what):
+def after_the_batch(gpu, cpu, cs, what, mod=uc):
+    """the oracle takes the case's frames one by one; then the maps are compared.  mod: as in frame_by_frame (the carve
+    blocks' verdicts are looked at where the case has them: update_cases)"""
     before_g, before_o = dump_set(gpu), dump_set(cpu)
-    _, cpos, _, _, verdict = uc.carve_blocks()
     alive = uc.keys(cs.blocks[0])
     for i, fr in enumerate(cs.frames):
         cpu.integrate(*fr.args())
         alive = still_alive(alive, cpu)
     assert_stats_equal(gpu, cpu, STATS)
     assert gpu.totals() == cpu.totals()  # (the first frame's carving among them)
-    compare(gpu, cpu, what, alive)
+    figures = compare(gpu, cpu, what, alive)
     after = dump_set(gpu)
-    assert np.array_equal(np.isin(uc.keys(cpos), uc.keys(after[0])), ~verdict), f"{what}: the carve blocks' verdicts"
+    if mod is uc:
+        _, cpos, _, _, verdict = uc.carve_blocks()
+        assert np.array_equal(np.isin(uc.keys(cpos), uc.keys(after[0])), ~verdict), f"{what}: the carve blocks' verdicts"
     # what none of the three frames updates keeps its words
     at, held = uc.align(before_g, after)
     upd = np.zeros(after[1][held].shape, bool)
     for fr in cs.frames:
-        upd |= uc.predict(after[0][held], fr).upd
+        upd |= mod.predict(after[0][held], fr).upd
     same = (uc.words(before_g, at[held]) == uc.words(after, held)).all(axis=-1)
     assert same[~upd].all() and (~upd).sum() >= 1000, f"{what}: {int((~same & ~upd).sum())} untouched voxels changed"
+    return figures
 
 
 @pytest.mark.parametrize("graph", ["1", "0"])

@@ -339,11 +339,12 @@ def words(s, rows=slice(None)):
     return np.stack([bits(s[1][rows]), np.ascontiguousarray(s[2][rows]).view(U32), bits(s[3][rows])], axis=-1)
 
 
-def untouched_unchanged(before, after, fr):
+def untouched_unchanged(before, after, fr, predict=None):
     """every voxel the frame does not update holds its three words bit for bit (blocks present on both sides).
-    Returns how many such voxels there were; raises AssertionError naming the first that changed."""
+    Returns how many such voxels there were; raises AssertionError naming the first that changed.
+    (predict: another case module's restatement, e.g. proj_cases.predict; this module's by default)"""
     at, held = align(before, after)
-    upd = predict(after[0][held], fr).upd
+    upd = (predict or globals()["predict"])(after[0][held], fr).upd
     wb, wa = words(before, at[held]), words(after, held)
     bad = (wb != wa).any(axis=-1) & ~upd
     assert not bad.any(), (f"{int(bad.sum())} voxels that the frame does not update changed, first at block "
