@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <algorithm>
 #include <atomic>
@@ -25,6 +26,7 @@
 #include "kernels_surface.h"
 #include "kernels_surface_mesh.h"
 #include "kernels_regions.h"
+#include "kernels_score.h"
 #include "kernels_fuse.h"
 #include "kernels_resample.h"
 #include "kernels_coarsen.h"
@@ -36,6 +38,7 @@
 #include "../../include/ratsdf_surface.h"
 #include "../../include/ratsdf_surface_mesh.h"
 #include "../../include/ratsdf_regions.h"
+#include "../../include/ratsdf_score.h"
 
 static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
 static_assert(ratsdf::kWsScanTile == (size_t)ratsdf::kScanTile, "scan_tiles() counts the tiles of kernels_mesh.h's scan");
@@ -258,6 +261,7 @@ struct EngineMem {
   Workspace ws_surface_mesh;  // ratsdf_surface_mesh*: surface_mesh_layout, per cell of the block grid
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
+  Workspace ws_score;         // ratsdf_score_labels: score_layout, one item
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
@@ -2067,3 +2071,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "coarsen.inc"  // ratsdf_coarsen_blocks_device / ratsdf_fuse_map_coarsened (include/ratsdf_coarsen.h)
 #include "surface_mesh.inc"  // ratsdf_surface_mesh[_device] (include/ratsdf_surface_mesh.h)
 #include "regions.inc"  // ratsdf_regions[_device] (include/ratsdf_regions.h)
+#include "score.inc"    // ratsdf_labelset_* / ratsdf_score_labels[_device] (include/ratsdf_score.h)

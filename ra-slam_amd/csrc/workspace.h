@@ -1,4 +1,4 @@
-// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc) carve their device
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc) and score.inc carve their device
 // workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
 // struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
 // written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
@@ -106,6 +106,15 @@ inline void regions_layout(WsCursor& c, size_t n, RegionsWork* w) {  // (offsets
   w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
   w->total = c.take_raw<uint32_t>(8);
   w->count = c.take_raw<long long>(8);
+}
+
+// label score (score.inc), n = 1: the score table of the host entry point (520 int64) | its int64 count, 16 bytes
+struct ScoreWork {
+  long long *score, *count;
+};
+inline void score_layout(WsCursor& c, size_t n, ScoreWork* w) {
+  w->score = c.take<long long>(4160 * n);
+  w->count = c.take_raw<long long>(16);
 }
 
 }  // namespace ratsdf

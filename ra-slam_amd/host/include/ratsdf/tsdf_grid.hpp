@@ -56,6 +56,12 @@ struct Api {
   // include/ratsdf_regions.h: likewise optional (not in the CPU oracle)
   int (*regions)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_regions_params*, int32_t*,
                  ratsdf_region**, size_t*) = nullptr;
+  // include/ratsdf_score.h: likewise optional (not in the CPU oracle)
+  int (*labelset_create)(ratsdf_engine*, const float*, const uint8_t*, size_t, float, ratsdf_labelset**) = nullptr;
+  int (*labelset_info_get)(const ratsdf_labelset*, ratsdf_labelset_info*) = nullptr;
+  int (*labelset_destroy)(ratsdf_labelset*) = nullptr;
+  int (*score_labels)(ratsdf_engine*, const ratsdf_labelset*, const ratsdf_score_params*, ratsdf_label_score*,
+                      ratsdf_voxel_label**, size_t*) = nullptr;
   // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
   int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
   int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
@@ -71,6 +77,35 @@ struct Api {
   // (the HIP engine); only test builds of this layer compile with another RATSDF_ABI_PREFIX to bind
   // the CPU oracle's copy of the ABI -- the product binaries have no switch for it.
   static const Api& Load(const char* path = nullptr, const char* prefix = RATSDF_ABI_PREFIX);
+};
+
+// Labelled points on the device (include/ratsdf_score.h): made by TSDFGrid::MakeLabelSet / TSDFSystem::MakeLabelSet,
+// immutable, destroyed with the object.  It belongs to the device, not to the grid that made it: any grid of that
+// device may score against it, and it may outlive them.
+class LabelSet {
+ public:
+  LabelSet() = default;
+  ~LabelSet() { reset(); }
+  LabelSet(LabelSet&& o) noexcept : api_(o.api_), set_(o.set_) { o.set_ = nullptr; }
+  LabelSet& operator=(LabelSet&& o) noexcept {
+    if (this != &o) {
+      reset();
+      api_ = o.api_, set_ = o.set_;
+      o.set_ = nullptr;
+    }
+    return *this;
+  }
+  LabelSet(const LabelSet&) = delete;
+  LabelSet& operator=(const LabelSet&) = delete;
+  void reset();
+  bool valid() const { return set_ != nullptr; }
+  ratsdf_labelset* handle() const { return set_; }
+  ratsdf_labelset_info info() const;  // (zeros when there is no set)
+
+ private:
+  friend class TSDFGrid;
+  const Api* api_ = nullptr;
+  ratsdf_labelset* set_ = nullptr;
 };
 
 class TSDFGrid {
@@ -140,6 +175,15 @@ class TSDFGrid {
   // No reference counterpart.
   int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
               std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);
+  // the map scored against labelled points (include/ratsdf_score.h).  MakeLabelSet: n points (xyz: 3 floats each,
+  // metres) with a label each (RATSDF_LABEL_*) into *out (what it held is destroyed first); cell: the edge of the
+  // search grid, 0 for 8 voxel sizes.  ScoreLabels: every voxel that params selects takes the label of its nearest
+  // point and counts against it in *out; *per_voxel (may be nullptr) receives one record per voxel in the order of
+  // GatherValidSemantic.  Return the status (also kept in last_status()); after a failure the set is not valid, *out
+  // is untouched and *per_voxel empty.  Replaces python_utils/scannet_eval/scanneteval.py on a DownloadAll file.
+  int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
+  int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
+                  std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
   // map fusion (include/ratsdf_fuse.h): another grid's map (same device, voxel size and truncation; only read), n
   // blocks in ratsdf_import_blocks' layout, or a checkpoint file merged into this map with the weighted-average voxel
   // update.  stats may be nullptr.  Return the status (also kept in last_status()); no reference counterpart.

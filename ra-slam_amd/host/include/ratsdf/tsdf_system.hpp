@@ -171,6 +171,10 @@ class TSDFSystem {
   // TSDFGrid::Regions under the engine's mutex, like ESDF
   int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
               std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);
+  // TSDFGrid::MakeLabelSet / TSDFGrid::ScoreLabels under the engine's mutex, like ESDF
+  int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
+  int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
+                  std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

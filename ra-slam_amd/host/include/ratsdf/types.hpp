@@ -22,6 +22,7 @@
 #include "../../../../include/ratsdf_surface.h"
 #include "../../../../include/ratsdf_surface_mesh.h"
 #include "../../../../include/ratsdf_regions.h"
+#include "../../../../include/ratsdf_score.h"
 
 namespace ratsdf {
 

@@ -31,6 +31,11 @@
 //          (float), red green blue (uchar), prob (float), weight (uchar); faces as lists of three int indices.  The box
 //          is tiled as for --surface-points; each tile's mesh is self-contained, so the vertices on a face two tiles
 //          share are written once per tile: duplicates there are accepted)]
+//          [--score-labels FILE [--score-cutoff P (0.5)] [--score-max-dist D (4 cells of the set)]
+//          [--score-tsdf-below T (0.1)] (after the last frame: the map scored against the labelled points of FILE, raw
+//          16-byte records {float x, y, z; uint32 label} with label 0 unannotated, 1 low-touch, 2 high-touch --
+//          include/ratsdf_score.h, what python_utils/scannet_eval/scanneteval.py computes from a DownloadAll file.
+//          Prints "score TP FP FN TN" with the four counts and "iou V" to stdout)]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -148,6 +153,46 @@ int write_surface_mesh(TSDFSystem& tsdf, float vs, const std::string& path) {
   return RATSDF_OK;
 }
 
+// the map scored against the labelled points of a file of {float x, y, z; uint32 label} records
+// (include/ratsdf_score.h); max_dist <= 0: four cells of the set
+int score_labels(TSDFSystem& tsdf, const std::string& path, float tsdf_below, float max_dist, float cutoff) {
+  std::ifstream f(path, std::ios::binary | std::ios::ate);
+  if (!f) return RATSDF_ERR_BAD_ARGUMENT;
+  const size_t bytes = (size_t)f.tellg();
+  if (bytes % 16) return RATSDF_ERR_BAD_ARGUMENT;
+  std::vector<uint32_t> raw(bytes / 4);
+  f.seekg(0);
+  f.read(reinterpret_cast<char*>(raw.data()), (std::streamsize)bytes);
+  if (!f) return RATSDF_ERR_BAD_ARGUMENT;
+  const size_t n = bytes / 16;
+  std::vector<float> xyz(3 * n);
+  std::vector<uint8_t> labels(n);
+  for (size_t i = 0; i < n; ++i) {
+    memcpy(&xyz[3 * i], &raw[4 * i], 12);
+    if (raw[4 * i + 3] > 2u) return RATSDF_ERR_BAD_ARGUMENT;
+    labels[i] = (uint8_t)raw[4 * i + 3];
+  }
+  LabelSet set;
+  int st = tsdf.MakeLabelSet(xyz.data(), labels.data(), n, 0.f, &set);
+  if (st != RATSDF_OK) return st;
+  ratsdf_score_params params;
+  memset(&params, 0, sizeof(params));
+  params.tsdf_below = tsdf_below;
+  params.max_dist = max_dist > 0.f ? max_dist : 4.f * set.info().cell;
+  params.p_cutoff = cutoff;
+  ratsdf_label_score score;
+  st = tsdf.ScoreLabels(set, params, &score);
+  if (st != RATSDF_OK) return st;
+  const double tp = (double)score.confusion[0], fp = (double)score.confusion[1], fn = (double)score.confusion[2];
+  fprintf(stderr, "[offline_eval] %zu labelled points (%lld kept); %lld voxels, %lld selected, %lld unmatched, "
+          "%lld unannotated\n", n, (long long)set.info().kept, (long long)score.voxels, (long long)score.selected,
+          (long long)score.unmatched, (long long)score.unannotated);
+  printf("score %lld %lld %lld %lld\n", (long long)score.confusion[0], (long long)score.confusion[1],
+         (long long)score.confusion[2], (long long)score.confusion[3]);
+  printf("iou %.17g\n", tp / (tp + fp + fn + 1e-15));  // scanneteval.py:100
+  return RATSDF_OK;
+}
+
 // the map coarsened `levels` times by two (include/ratsdf_coarsen.h) as a checkpoint: a chain of grids of twice the
 // voxel size each, a level destroyed as soon as the next one exists
 int write_coarse_map(TSDFSystem& tsdf, const Api& api, float vs, float trunc, int device, int levels,
@@ -179,7 +224,8 @@ int main(int argc, char** argv) {
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
   std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points, save_coarse_map;
-  std::string surface_mesh;
+  std::string surface_mesh, score_file;
+  float score_cutoff = 0.5f, score_max_dist = 0.f, score_tsdf_below = 0.1f;
   int coarse_levels = 1;
   bool reader_only = false, dump_raw_color = false;
   for (int i = 2; i < argc; ++i) {
@@ -207,6 +253,10 @@ int main(int argc, char** argv) {
     else if (a == "--fuse-map") fuse_map = next();
     else if (a == "--surface-points") surface_points = next();
     else if (a == "--surface-mesh") surface_mesh = next();
+    else if (a == "--score-labels") score_file = next();
+    else if (a == "--score-cutoff") score_cutoff = strtof(next(), nullptr);
+    else if (a == "--score-max-dist") score_max_dist = strtof(next(), nullptr);
+    else if (a == "--score-tsdf-below") score_tsdf_below = strtof(next(), nullptr);
     else if (a == "--save-coarse-map") save_coarse_map = next();
     else if (a == "--coarse-levels") coarse_levels = atoi(next());
     else if (a == "--first-frame") first_frame = atoi(next());
@@ -341,6 +391,14 @@ int main(int argc, char** argv) {
         const int st = write_surface_mesh(*tsdf, voxel_size, surface_mesh);
         if (st != RATSDF_OK) {
           fprintf(stderr, "[offline_eval] --surface-mesh %s: %s\n", surface_mesh.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
+      if (!score_file.empty()) {
+        const int st = score_labels(*tsdf, score_file, score_tsdf_below, score_max_dist, score_cutoff);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --score-labels %s: %s\n", score_file.c_str(),
                   Api::Load(lib).status_string(st));
           return 1;
         }

@@ -87,6 +87,10 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
   api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
   api.regions = reinterpret_cast<decltype(api.regions)>(opt_sym("regions"));
+  api.labelset_create = reinterpret_cast<decltype(api.labelset_create)>(opt_sym("labelset_create"));
+  api.labelset_info_get = reinterpret_cast<decltype(api.labelset_info_get)>(opt_sym("labelset_info_get"));
+  api.labelset_destroy = reinterpret_cast<decltype(api.labelset_destroy)>(opt_sym("labelset_destroy"));
+  api.score_labels = reinterpret_cast<decltype(api.score_labels)>(opt_sym("score_labels"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -339,6 +343,43 @@ int TSDFGrid::Regions(const int32_t origin[3], const int32_t dims[3], const rats
     labels->clear();
   }
   if (r) api_->free_buffer(r);
+  return status_;
+}
+
+void LabelSet::reset() {
+  if (set_ && api_ && api_->labelset_destroy) api_->labelset_destroy(set_);
+  set_ = nullptr;
+}
+
+ratsdf_labelset_info LabelSet::info() const {
+  ratsdf_labelset_info i;
+  memset(&i, 0, sizeof(i));
+  if (set_ && api_ && api_->labelset_info_get) api_->labelset_info_get(set_, &i);
+  return i;
+}
+
+int TSDFGrid::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {
+  if (out) out->reset();
+  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_labelset* s = nullptr;
+  note(api_->labelset_create ? api_->labelset_create(engine_, xyz, labels, n, cell, &s) : RATSDF_ERR_NOT_IMPLEMENTED,
+       "MakeLabelSet");
+  if (status_ == RATSDF_OK) out->api_ = api_, out->set_ = s;
+  return status_;
+}
+
+int TSDFGrid::ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
+                          std::vector<ratsdf_voxel_label>* per_voxel) {
+  if (per_voxel) per_voxel->clear();
+  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_voxel_label* v = nullptr;
+  size_t nv = 0;
+  note(api_->score_labels ? api_->score_labels(engine_, set.handle(), &params, out, per_voxel ? &v : nullptr,
+                                               per_voxel ? &nv : nullptr)
+                          : RATSDF_ERR_NOT_IMPLEMENTED,
+       "ScoreLabels");
+  if (status_ == RATSDF_OK && v) per_voxel->assign(v, v + nv);
+  if (v) api_->free_buffer(v);
   return status_;
 }
 
@@ -665,6 +706,17 @@ int TSDFSystem::Regions(const int32_t origin[3], const int32_t dims[3], const ra
                         std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.Regions(origin, dims, params, labels, regions);
+}
+
+int TSDFSystem::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.MakeLabelSet(xyz, labels, n, cell, out);
+}
+
+int TSDFSystem::ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
+                            std::vector<ratsdf_voxel_label>* per_voxel) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.ScoreLabels(set, params, out, per_voxel);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

@@ -10,6 +10,8 @@ from . import _abi
 from ._abi import (BLOCK_DTYPE, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED, ESDF_STATE_UNKNOWN, ESDF_UNKNOWN_OCCUPIED,
                    REGION_DTYPE, RGBW_DTYPE, SAMPLE_DTYPE, SURFACE_DTYPE, VOXEL_SEGM_DTYPE, VOXEL_TSDF_DTYPE, Bounds,
                    Engine, Group, Intrinsics, Library, Pose, RatsdfError, RegionsParams, voxel_box)
+from ._abi import (LABEL_HIGH, LABEL_IGNORE, LABEL_LOW, LABEL_SCORE_DTYPE, VOXEL_LABEL_DTYPE, LabelScore, LabelSet,
+                   ScoreParams)
 from .pose import compose, identity_pose, invert, pose_from_matrix
 
 _PKG_ROOT = Path(__file__).resolve().parent.parent
@@ -48,4 +50,5 @@ __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "P
            "RatsdfError", "map_file_info", "pose_from_matrix", "compose", "invert", "identity_pose", "BLOCK_DTYPE",
            "RGBW_DTYPE", "SAMPLE_DTYPE", "VOXEL_TSDF_DTYPE", "VOXEL_SEGM_DTYPE", "LIB_PATH", "voxel_box",
            "ESDF_UNKNOWN_OCCUPIED", "ESDF_STATE_UNKNOWN", "ESDF_STATE_FREE", "ESDF_STATE_OCCUPIED",
-           "SURFACE_DTYPE", "REGION_DTYPE", "RegionsParams"]
+           "SURFACE_DTYPE", "REGION_DTYPE", "RegionsParams", "LABEL_SCORE_DTYPE", "VOXEL_LABEL_DTYPE", "ScoreParams",
+           "LabelSet", "LabelScore", "LABEL_IGNORE", "LABEL_LOW", "LABEL_HIGH"]

@@ -138,6 +138,117 @@ class RegionsParams(C.Structure):
     _fields_ = [("occupied_below", C.c_float), ("min_prob", C.c_float), ("states", C.c_uint32), ("flags", C.c_uint32)]
 
 
+# include/ratsdf_score.h (label sets and the map's score against them): handled like ESDF_SYMBOLS
+SCORE_SYMBOLS = ["labelset_create", "labelset_create_device", "labelset_info_get", "labelset_destroy", "score_labels",
+                 "score_labels_device"]
+LABEL_IGNORE, LABEL_LOW, LABEL_HIGH = 0, 1, 2
+# ratsdf_label_score (4160 bytes) and ratsdf_voxel_label (8 bytes)
+LABEL_SCORE_DTYPE = np.dtype([("voxels", "<i8"), ("selected", "<i8"), ("unmatched", "<i8"), ("unannotated", "<i8"),
+                              ("confusion", "<i8", (4,)), ("hist", "<i8", (2, 256))])
+VOXEL_LABEL_DTYPE = np.dtype([("nearest", "<i4"), ("dist2", "<f4")])
+assert LABEL_SCORE_DTYPE.itemsize == 4160 and VOXEL_LABEL_DTYPE.itemsize == 8
+
+
+class ScoreParams(C.Structure):
+    """ratsdf_score_params"""
+    _fields_ = [("tsdf_below", C.c_float), ("max_dist", C.c_float), ("p_cutoff", C.c_float),
+                ("min_weight", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class LabelSetInfo(C.Structure):
+    """ratsdf_labelset_info"""
+    _fields_ = [("points", C.c_int64), ("kept", C.c_int64), ("cell", C.c_float), ("origin", C.c_float * 3),
+                ("cells", C.c_int32 * 3), ("reserved", C.c_uint32)]
+
+
+class LabelSet:
+    """labelled points on the device (ratsdf_labelset): built by Engine.label_set, immutable, usable by every engine of
+    the same device until close()"""
+
+    def __init__(self, lib, handle):
+        self.lib, self._h = lib, handle
+
+    @property
+    def info(self):
+        i = LabelSetInfo()
+        _check(self.lib.fn["labelset_info_get"](self._h, C.byref(i)), "labelset_info_get")
+        return {"points": i.points, "kept": i.kept, "cell": i.cell, "origin": tuple(i.origin), "cells": tuple(i.cells)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.fn["labelset_destroy"](self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class LabelScore:
+    """the counts of ratsdf_label_score with the reference's figures (scanneteval.py:95-124: IoU, precision and recall
+    with its 1e-15 in the denominator, the voxel accuracy without, so NaN when nothing was counted).  Counts of shard
+    ranks add: a + b."""
+
+    def __init__(self, record):
+        self.record = np.array(record, dtype=LABEL_SCORE_DTYPE).reshape(())
+
+    voxels = property(lambda self: int(self.record["voxels"]))
+    selected = property(lambda self: int(self.record["selected"]))
+    unmatched = property(lambda self: int(self.record["unmatched"]))
+    unannotated = property(lambda self: int(self.record["unannotated"]))
+    confusion = property(lambda self: tuple(int(v) for v in self.record["confusion"]))
+    hist = property(lambda self: self.record["hist"])
+
+    @staticmethod
+    def _figures(tp, fp, fn, tn):
+        return {"iou": tp / (tp + fp + fn + 1e-15), "precision": tp / (tp + fp + 1e-15),
+                "recall": tp / (tp + fn + 1e-15),
+                "accuracy": (tp + tn) / (tp + tn + fp + fn) if tp + tn + fp + fn else float("nan")}
+
+    iou = property(lambda self: self._figures(*self.confusion)["iou"])
+    precision = property(lambda self: self._figures(*self.confusion)["precision"])
+    recall = property(lambda self: self._figures(*self.confusion)["recall"])
+    accuracy = property(lambda self: self._figures(*self.confusion)["accuracy"])
+
+    def pr_curve(self):
+        """the figures at every cutoff k / 256, k = 0..255, from the histogram: a voxel in bin b has a probability in
+        [b / 256, (b + 1) / 256), so it is predicted high at cutoff k / 256 exactly when b >= k -- except that a
+        probability EQUAL to k / 256 is not above it: the curve is that of the test prob >= k / 256 for k > 0 and
+        counts bin 0 (zero, negative and NaN probabilities included) as high at k = 0.  Returns a dict of arrays
+        (cutoff, tp, fp, fn, tn, iou, precision, recall, accuracy)."""
+        h = self.hist.astype(np.int64)
+        above = np.cumsum(h[:, ::-1], axis=1)[:, ::-1]           # voxels in bins >= k
+        total = h.sum(axis=1, keepdims=True)
+        fp, tp = above[0], above[1]
+        tn, fn = total[0] - fp, total[1] - tp
+        out = {"cutoff": np.arange(256) / 256.0, "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out.update({"iou": tp / (tp + fp + fn + 1e-15), "precision": tp / (tp + fp + 1e-15),
+                        "recall": tp / (tp + fn + 1e-15), "accuracy": (tp + tn) / (tp + tn + fp + fn)})
+        return out
+
+    def __add__(self, other):
+        r = self.record.copy()
+        for k in LABEL_SCORE_DTYPE.names:
+            r[k] = self.record[k] + other.record[k]
+        return LabelScore(r)
+
+    def __eq__(self, other):
+        return isinstance(other, LabelScore) and self.record.tobytes() == other.record.tobytes()
+
+    def __repr__(self):
+        return (f"LabelScore(voxels={self.voxels}, selected={self.selected}, unmatched={self.unmatched}, "
+                f"unannotated={self.unannotated}, confusion={self.confusion}, iou={self.iou:.6f})")
+
+
 class _OwnedBuffer:
     """a result buffer handed over by the library (malloc'ed there): exposes it through the array interface and gives
     it back with ratsdf_free_buffer when the last array built on it is collected"""
@@ -297,6 +408,19 @@ class Library:
                 box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(RegionsParams)]
                 f.argtypes = box + {"regions": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
                                     "regions_device": [vp, vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in SCORE_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                sp = C.POINTER(ScoreParams)
+                f.argtypes = {"labelset_create": [vp, vp, vp, C.c_size_t, C.c_float, C.POINTER(vp)],
+                              "labelset_create_device": [vp, vp, vp, C.c_size_t, C.c_float, C.POINTER(vp)],
+                              "labelset_info_get": [vp, C.POINTER(LabelSetInfo)], "labelset_destroy": [vp],
+                              "score_labels": [vp, vp, sp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
+                              "score_labels_device": [vp, vp, sp, vp, vp, C.c_int64, vp]}[s]
             self.fn[s] = f
 
         for s in FUSE_SYMBOLS:
@@ -799,6 +923,57 @@ class Engine:
         if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
             return int(d_count.numpy().view(np.int64).reshape(-1)[0])
         return None                          # a raw pointer: the caller reads it
+
+    def label_set(self, points, labels, cell=0.0):
+        """a LabelSet of n labelled points (ratsdf_labelset_create, include/ratsdf_score.h): points [n, 3] float32
+        metres, labels [n] uint8 of LABEL_IGNORE / LABEL_LOW / LABEL_HIGH.  cell: the edge of the search grid's cells,
+        0 for 8 voxel sizes of this engine.  With `points` and `labels` on the device (torch tensors or
+        devmem.DeviceArray: float32 [n, 3] and uint8 [n], contiguous) it is built from them in place."""
+        h = C.c_void_p()
+        if hasattr(points, "data_ptr"):
+            n = int(labels.shape[0]) if hasattr(labels, "shape") else int(len(labels))
+            _check(self.lib.fn["labelset_create_device"](self._h, points.data_ptr() or None, labels.data_ptr() or None,
+                                                         n, C.c_float(float(cell)), C.byref(h)),
+                   "labelset_create_device")
+            return LabelSet(self.lib, h)
+        xyz = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        if lab.shape[0] != xyz.shape[0]:
+            raise ValueError("one label per point")
+        _check(self.lib.fn["labelset_create"](self._h, xyz.ctypes.data if len(xyz) else None,
+                                              lab.ctypes.data if len(lab) else None, len(xyz), C.c_float(float(cell)),
+                                              C.byref(h)), "labelset_create")
+        return LabelSet(self.lib, h)
+
+    def score_labels(self, label_set, tsdf_below=0.1, max_dist=None, p_cutoff=0.5, min_weight=0, per_voxel=False):
+        """the map scored against a LabelSet (ratsdf_score_labels): every voxel with |tsdf| < tsdf_below and weight >=
+        min_weight takes the label of its nearest point within max_dist (default: 4 cells of the set) and counts by
+        prob > p_cutoff against it.  Returns a LabelScore, with per_voxel also VOXEL_LABEL_DTYPE records in the order
+        of gather_valid_semantic()."""
+        if max_dist is None:
+            max_dist = 4.0 * label_set.info["cell"]
+        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
+        rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
+        p, m = C.c_void_p(), C.c_size_t()
+        _check(self.lib.fn["score_labels"](self._h, label_set._h, C.byref(params), rec.ctypes.data,
+                                           C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None),
+               "score_labels")
+        score = LabelScore(rec)
+        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+
+    def score_labels_device(self, label_set, d_score, d_per_voxel, capacity, d_count, tsdf_below=0.1, max_dist=None,
+                            p_cutoff=0.5, min_weight=0):
+        """score_labels() into DEVICE buffers, asynchronous on the engine's stream: the 4160-byte score to d_score, at
+        most `capacity` 8-byte per-voxel records to d_per_voxel (0 for none) and the number of voxels as an int64 to
+        d_count; all 8-byte aligned.  Each buffer: a torch tensor, a devmem.DeviceArray or a raw pointer.  Returns
+        nothing: synchronize() before reading."""
+        if max_dist is None:
+            max_dist = 4.0 * label_set.info["cell"]
+        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_score, d_per_voxel, d_count)]
+        _check(self.lib.fn["score_labels_device"](self._h, label_set._h, C.byref(params), ptr[0] or None,
+                                                  ptr[1] or None, int(capacity), ptr[2] or None),
+               "score_labels_device")
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,
