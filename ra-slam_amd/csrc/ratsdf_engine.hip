@@ -27,6 +27,7 @@
 #include "kernels_surface_mesh.h"
 #include "kernels_regions.h"
 #include "kernels_score.h"
+#include "kernels_score_mesh.h"
 #include "kernels_fuse.h"
 #include "kernels_resample.h"
 #include "kernels_coarsen.h"
@@ -39,6 +40,7 @@
 #include "../../include/ratsdf_surface_mesh.h"
 #include "../../include/ratsdf_regions.h"
 #include "../../include/ratsdf_score.h"
+#include "../../include/ratsdf_score_mesh.h"
 
 static_assert(sizeof(ratsdf_sample) == 32 && offsetof(ratsdf_sample, flags) == 25, "ratsdf_sample layout");
 static_assert(ratsdf::kWsScanTile == (size_t)ratsdf::kScanTile, "scan_tiles() counts the tiles of kernels_mesh.h's scan");
@@ -262,6 +264,7 @@ struct EngineMem {
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
   Workspace ws_score;         // ratsdf_score_labels: score_layout, one item
+  Workspace ws_score_mesh;    // ratsdf_score_mesh: score_mesh_layout, one item
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
@@ -2072,3 +2075,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "surface_mesh.inc"  // ratsdf_surface_mesh[_device] (include/ratsdf_surface_mesh.h)
 #include "regions.inc"  // ratsdf_regions[_device] (include/ratsdf_regions.h)
 #include "score.inc"    // ratsdf_labelset_* / ratsdf_score_labels[_device] (include/ratsdf_score.h)
+#include "score_mesh.inc"  // ratsdf_labelmesh_* / ratsdf_score_mesh[_device] (include/ratsdf_score_mesh.h)

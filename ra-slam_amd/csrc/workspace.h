@@ -1,4 +1,4 @@
-// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc) and score.inc carve their device
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc), score.inc and score_mesh.inc carve their device
 // workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
 // struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
 // written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
@@ -113,6 +113,16 @@ struct ScoreWork {
   long long *score, *count;
 };
 inline void score_layout(WsCursor& c, size_t n, ScoreWork* w) {
+  w->score = c.take<long long>(4160 * n);
+  w->count = c.take_raw<long long>(16);
+}
+
+// label score against a mesh (score_mesh.inc), n = 1: as score_layout, a buffer of its own -- the score table of the
+// host entry point (520 int64) | its int64 count, 16 bytes
+struct ScoreMeshWork {
+  long long *score, *count;
+};
+inline void score_mesh_layout(WsCursor& c, size_t n, ScoreMeshWork* w) {
   w->score = c.take<long long>(4160 * n);
   w->count = c.take_raw<long long>(16);
 }

@@ -62,6 +62,13 @@ struct Api {
   int (*labelset_destroy)(ratsdf_labelset*) = nullptr;
   int (*score_labels)(ratsdf_engine*, const ratsdf_labelset*, const ratsdf_score_params*, ratsdf_label_score*,
                       ratsdf_voxel_label**, size_t*) = nullptr;
+  // include/ratsdf_score_mesh.h: likewise optional (not in the CPU oracle)
+  int (*labelmesh_create)(ratsdf_engine*, const float*, const uint8_t*, size_t, const int32_t*, size_t, float,
+                          ratsdf_labelmesh**) = nullptr;
+  int (*labelmesh_info_get)(const ratsdf_labelmesh*, ratsdf_labelmesh_info*) = nullptr;
+  int (*labelmesh_destroy)(ratsdf_labelmesh*) = nullptr;
+  int (*score_mesh)(ratsdf_engine*, const ratsdf_labelmesh*, const ratsdf_score_params*, ratsdf_label_score*,
+                    ratsdf_voxel_label**, size_t*) = nullptr;
   // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
   int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
   int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
@@ -106,6 +113,35 @@ class LabelSet {
   friend class TSDFGrid;
   const Api* api_ = nullptr;
   ratsdf_labelset* set_ = nullptr;
+};
+
+// A labelled triangle mesh on the device (include/ratsdf_score_mesh.h): made by TSDFGrid::MakeLabelMesh /
+// TSDFSystem::MakeLabelMesh, immutable, destroyed with the object.  Like a LabelSet it belongs to the device, not to
+// the grid that made it.
+class LabelMesh {
+ public:
+  LabelMesh() = default;
+  ~LabelMesh() { reset(); }
+  LabelMesh(LabelMesh&& o) noexcept : api_(o.api_), mesh_(o.mesh_) { o.mesh_ = nullptr; }
+  LabelMesh& operator=(LabelMesh&& o) noexcept {
+    if (this != &o) {
+      reset();
+      api_ = o.api_, mesh_ = o.mesh_;
+      o.mesh_ = nullptr;
+    }
+    return *this;
+  }
+  LabelMesh(const LabelMesh&) = delete;
+  LabelMesh& operator=(const LabelMesh&) = delete;
+  void reset();
+  bool valid() const { return mesh_ != nullptr; }
+  ratsdf_labelmesh* handle() const { return mesh_; }
+  ratsdf_labelmesh_info info() const;  // (zeros when there is no mesh)
+
+ private:
+  friend class TSDFGrid;
+  const Api* api_ = nullptr;
+  ratsdf_labelmesh* mesh_ = nullptr;
 };
 
 class TSDFGrid {
@@ -184,6 +220,16 @@ class TSDFGrid {
   int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
   int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
                   std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
+  // the map scored against a labelled triangle mesh (include/ratsdf_score_mesh.h).  MakeLabelMesh: n_vertices points
+  // (xyz: 3 floats each, metres) with a label each (RATSDF_LABEL_*) and n_triangles index triples into *out (what it
+  // held is destroyed first); a triangle carries the label of its first vertex.  ScoreMesh: ScoreLabels with the
+  // nearest triangle in place of the nearest point; per_voxel->nearest is a triangle's index.  Return the status (also
+  // kept in last_status()); after a failure the mesh is not valid, *out is untouched and *per_voxel empty.  Replaces
+  // scanneteval.py's nn_method="mesh" on a DownloadAll file.
+  int MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri, size_t n_triangles,
+                    float cell, LabelMesh* out);
+  int ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
+                std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
   // map fusion (include/ratsdf_fuse.h): another grid's map (same device, voxel size and truncation; only read), n
   // blocks in ratsdf_import_blocks' layout, or a checkpoint file merged into this map with the weighted-average voxel
   // update.  stats may be nullptr.  Return the status (also kept in last_status()); no reference counterpart.

@@ -175,6 +175,11 @@ class TSDFSystem {
   int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
   int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
                   std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
+  // TSDFGrid::MakeLabelMesh / TSDFGrid::ScoreMesh under the engine's mutex, like MakeLabelSet / ScoreLabels
+  int MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri, size_t n_triangles,
+                    float cell, LabelMesh* out);
+  int ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
+                std::vector<ratsdf_voxel_label>* per_voxel = nullptr);
   size_t QueueSize();
   int NumActiveBlock();
   size_t frames_integrated();

@@ -36,6 +36,10 @@
 //          16-byte records {float x, y, z; uint32 label} with label 0 unannotated, 1 low-touch, 2 high-touch --
 //          include/ratsdf_score.h, what python_utils/scannet_eval/scanneteval.py computes from a DownloadAll file.
 //          Prints "score TP FP FN TN" with the four counts and "iou V" to stdout)]
+//          [--score-mesh FILE (likewise, against the labelled triangle mesh of FILE -- include/ratsdf_score_mesh.h, the
+//          script's nn_method="mesh"; raw little-endian: int64 V, int64 T, then V records {float x, y, z; uint32 label},
+//          then T records of three int32 vertex indices.  The other --score-* options apply.  Prints the same two
+//          lines; given together with --score-labels the lines of the two are prefixed "points " and "mesh ")]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -155,7 +159,8 @@ int write_surface_mesh(TSDFSystem& tsdf, float vs, const std::string& path) {
 
 // the map scored against the labelled points of a file of {float x, y, z; uint32 label} records
 // (include/ratsdf_score.h); max_dist <= 0: four cells of the set
-int score_labels(TSDFSystem& tsdf, const std::string& path, float tsdf_below, float max_dist, float cutoff) {
+int score_labels(TSDFSystem& tsdf, const std::string& path, float tsdf_below, float max_dist, float cutoff,
+                 const char* prefix) {
   std::ifstream f(path, std::ios::binary | std::ios::ate);
   if (!f) return RATSDF_ERR_BAD_ARGUMENT;
   const size_t bytes = (size_t)f.tellg();
@@ -187,9 +192,58 @@ int score_labels(TSDFSystem& tsdf, const std::string& path, float tsdf_below, fl
   fprintf(stderr, "[offline_eval] %zu labelled points (%lld kept); %lld voxels, %lld selected, %lld unmatched, "
           "%lld unannotated\n", n, (long long)set.info().kept, (long long)score.voxels, (long long)score.selected,
           (long long)score.unmatched, (long long)score.unannotated);
-  printf("score %lld %lld %lld %lld\n", (long long)score.confusion[0], (long long)score.confusion[1],
+  printf("%sscore %lld %lld %lld %lld\n", prefix, (long long)score.confusion[0], (long long)score.confusion[1],
          (long long)score.confusion[2], (long long)score.confusion[3]);
-  printf("iou %.17g\n", tp / (tp + fp + fn + 1e-15));  // scanneteval.py:100
+  printf("%siou %.17g\n", prefix, tp / (tp + fp + fn + 1e-15));  // scanneteval.py:100
+  return RATSDF_OK;
+}
+
+// the map scored against the labelled triangle mesh of a file: int64 V, int64 T, V records {float x, y, z; uint32
+// label}, T records of three int32 (include/ratsdf_score_mesh.h); max_dist <= 0: four cells of the set
+int score_mesh(TSDFSystem& tsdf, const std::string& path, float tsdf_below, float max_dist, float cutoff,
+               const char* prefix) {
+  std::ifstream f(path, std::ios::binary | std::ios::ate);
+  if (!f) return RATSDF_ERR_BAD_ARGUMENT;
+  const size_t bytes = (size_t)f.tellg();
+  int64_t head[2] = {0, 0};
+  f.seekg(0);
+  f.read(reinterpret_cast<char*>(head), 16);
+  if (!f || head[0] < 0 || head[1] < 0 || head[0] > ((int64_t)1 << 26) || head[1] > ((int64_t)1 << 26))
+    return RATSDF_ERR_BAD_ARGUMENT;
+  const size_t nv = (size_t)head[0], nt = (size_t)head[1];
+  if (bytes != 16 + 16 * nv + 12 * nt) return RATSDF_ERR_BAD_ARGUMENT;
+  std::vector<uint32_t> raw(4 * nv);
+  std::vector<int32_t> tri(3 * nt);
+  f.read(reinterpret_cast<char*>(raw.data()), (std::streamsize)(16 * nv));
+  f.read(reinterpret_cast<char*>(tri.data()), (std::streamsize)(12 * nt));
+  if (!f) return RATSDF_ERR_BAD_ARGUMENT;
+  std::vector<float> xyz(3 * nv);
+  std::vector<uint8_t> labels(nv);
+  for (size_t i = 0; i < nv; ++i) {
+    memcpy(&xyz[3 * i], &raw[4 * i], 12);
+    if (raw[4 * i + 3] > 2u) return RATSDF_ERR_BAD_ARGUMENT;
+    labels[i] = (uint8_t)raw[4 * i + 3];
+  }
+  LabelMesh mesh;
+  int st = tsdf.MakeLabelMesh(xyz.data(), labels.data(), nv, tri.data(), nt, 0.f, &mesh);
+  if (st != RATSDF_OK) return st;
+  const ratsdf_labelmesh_info info = mesh.info();
+  ratsdf_score_params params;
+  memset(&params, 0, sizeof(params));
+  params.tsdf_below = tsdf_below;
+  params.max_dist = max_dist > 0.f ? max_dist : 4.f * info.cell;
+  params.p_cutoff = cutoff;
+  ratsdf_label_score score;
+  st = tsdf.ScoreMesh(mesh, params, &score);
+  if (st != RATSDF_OK) return st;
+  const double tp = (double)score.confusion[0], fp = (double)score.confusion[1], fn = (double)score.confusion[2];
+  fprintf(stderr, "[offline_eval] %zu labelled triangles (%lld kept, %lld of mixed labels, %lld cell references); "
+          "%lld voxels, %lld selected, %lld unmatched, %lld unannotated\n", nt, (long long)info.kept,
+          (long long)info.mixed, (long long)info.refs, (long long)score.voxels, (long long)score.selected,
+          (long long)score.unmatched, (long long)score.unannotated);
+  printf("%sscore %lld %lld %lld %lld\n", prefix, (long long)score.confusion[0], (long long)score.confusion[1],
+         (long long)score.confusion[2], (long long)score.confusion[3]);
+  printf("%siou %.17g\n", prefix, tp / (tp + fp + fn + 1e-15));  // scanneteval.py:100
   return RATSDF_OK;
 }
 
@@ -224,7 +278,7 @@ int main(int argc, char** argv) {
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
   std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points, save_coarse_map;
-  std::string surface_mesh, score_file;
+  std::string surface_mesh, score_file, score_mesh_file;
   float score_cutoff = 0.5f, score_max_dist = 0.f, score_tsdf_below = 0.1f;
   int coarse_levels = 1;
   bool reader_only = false, dump_raw_color = false;
@@ -254,6 +308,7 @@ int main(int argc, char** argv) {
     else if (a == "--surface-points") surface_points = next();
     else if (a == "--surface-mesh") surface_mesh = next();
     else if (a == "--score-labels") score_file = next();
+    else if (a == "--score-mesh") score_mesh_file = next();
     else if (a == "--score-cutoff") score_cutoff = strtof(next(), nullptr);
     else if (a == "--score-max-dist") score_max_dist = strtof(next(), nullptr);
     else if (a == "--score-tsdf-below") score_tsdf_below = strtof(next(), nullptr);
@@ -395,10 +450,21 @@ int main(int argc, char** argv) {
           return 1;
         }
       }
+      const bool score_both = !score_file.empty() && !score_mesh_file.empty();
       if (!score_file.empty()) {
-        const int st = score_labels(*tsdf, score_file, score_tsdf_below, score_max_dist, score_cutoff);
+        const int st = score_labels(*tsdf, score_file, score_tsdf_below, score_max_dist, score_cutoff,
+                                    score_both ? "points " : "");
         if (st != RATSDF_OK) {
           fprintf(stderr, "[offline_eval] --score-labels %s: %s\n", score_file.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
+      if (!score_mesh_file.empty()) {
+        const int st = score_mesh(*tsdf, score_mesh_file, score_tsdf_below, score_max_dist, score_cutoff,
+                                  score_both ? "mesh " : "");
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --score-mesh %s: %s\n", score_mesh_file.c_str(),
                   Api::Load(lib).status_string(st));
           return 1;
         }

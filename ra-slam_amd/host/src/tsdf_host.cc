@@ -91,6 +91,10 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.labelset_info_get = reinterpret_cast<decltype(api.labelset_info_get)>(opt_sym("labelset_info_get"));
   api.labelset_destroy = reinterpret_cast<decltype(api.labelset_destroy)>(opt_sym("labelset_destroy"));
   api.score_labels = reinterpret_cast<decltype(api.score_labels)>(opt_sym("score_labels"));
+  api.labelmesh_create = reinterpret_cast<decltype(api.labelmesh_create)>(opt_sym("labelmesh_create"));
+  api.labelmesh_info_get = reinterpret_cast<decltype(api.labelmesh_info_get)>(opt_sym("labelmesh_info_get"));
+  api.labelmesh_destroy = reinterpret_cast<decltype(api.labelmesh_destroy)>(opt_sym("labelmesh_destroy"));
+  api.score_mesh = reinterpret_cast<decltype(api.score_mesh)>(opt_sym("score_mesh"));
   return loaded.emplace(key, api).first->second;
 }
 
@@ -378,6 +382,46 @@ int TSDFGrid::ScoreLabels(const LabelSet& set, const ratsdf_score_params& params
                                                per_voxel ? &nv : nullptr)
                           : RATSDF_ERR_NOT_IMPLEMENTED,
        "ScoreLabels");
+  if (status_ == RATSDF_OK && v) per_voxel->assign(v, v + nv);
+  if (v) api_->free_buffer(v);
+  return status_;
+}
+
+void LabelMesh::reset() {
+  if (mesh_ && api_ && api_->labelmesh_destroy) api_->labelmesh_destroy(mesh_);
+  mesh_ = nullptr;
+}
+
+ratsdf_labelmesh_info LabelMesh::info() const {
+  ratsdf_labelmesh_info i;
+  memset(&i, 0, sizeof(i));
+  if (mesh_ && api_ && api_->labelmesh_info_get) api_->labelmesh_info_get(mesh_, &i);
+  return i;
+}
+
+int TSDFGrid::MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri,
+                            size_t n_triangles, float cell, LabelMesh* out) {
+  if (out) out->reset();
+  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_labelmesh* m = nullptr;
+  note(api_->labelmesh_create
+           ? api_->labelmesh_create(engine_, xyz, labels, n_vertices, tri, n_triangles, cell, &m)
+           : RATSDF_ERR_NOT_IMPLEMENTED,
+       "MakeLabelMesh");
+  if (status_ == RATSDF_OK) out->api_ = api_, out->mesh_ = m;
+  return status_;
+}
+
+int TSDFGrid::ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
+                        std::vector<ratsdf_voxel_label>* per_voxel) {
+  if (per_voxel) per_voxel->clear();
+  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_voxel_label* v = nullptr;
+  size_t nv = 0;
+  note(api_->score_mesh ? api_->score_mesh(engine_, mesh.handle(), &params, out, per_voxel ? &v : nullptr,
+                                           per_voxel ? &nv : nullptr)
+                        : RATSDF_ERR_NOT_IMPLEMENTED,
+       "ScoreMesh");
   if (status_ == RATSDF_OK && v) per_voxel->assign(v, v + nv);
   if (v) api_->free_buffer(v);
   return status_;
@@ -717,6 +761,18 @@ int TSDFSystem::ScoreLabels(const LabelSet& set, const ratsdf_score_params& para
                             std::vector<ratsdf_voxel_label>* per_voxel) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.ScoreLabels(set, params, out, per_voxel);
+}
+
+int TSDFSystem::MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri,
+                              size_t n_triangles, float cell, LabelMesh* out) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.MakeLabelMesh(xyz, labels, n_vertices, tri, n_triangles, cell, out);
+}
+
+int TSDFSystem::ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
+                          std::vector<ratsdf_voxel_label>* per_voxel) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.ScoreMesh(mesh, params, out, per_voxel);
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {

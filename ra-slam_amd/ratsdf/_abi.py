@@ -249,6 +249,51 @@ class LabelScore:
                 f"unannotated={self.unannotated}, confusion={self.confusion}, iou={self.iou:.6f})")
 
 
+# include/ratsdf_score_mesh.h (labelled triangle meshes and the map's score against them): handled like SCORE_SYMBOLS
+SCORE_MESH_SYMBOLS = ["labelmesh_create", "labelmesh_create_device", "labelmesh_info_get", "labelmesh_destroy",
+                      "score_mesh", "score_mesh_device"]
+LABELMESH_MAX_REFS = 1 << 25
+
+
+class LabelMeshInfo(C.Structure):
+    """ratsdf_labelmesh_info"""
+    _fields_ = [("vertices", C.c_int64), ("triangles", C.c_int64), ("kept", C.c_int64), ("mixed", C.c_int64),
+                ("refs", C.c_int64), ("cell", C.c_float), ("origin", C.c_float * 3), ("cells", C.c_int32 * 3),
+                ("reserved", C.c_uint32)]
+
+
+class LabelMesh:
+    """a labelled triangle mesh on the device (ratsdf_labelmesh): built by Engine.label_mesh, immutable, usable by
+    every engine of the same device until close()"""
+
+    def __init__(self, lib, handle):
+        self.lib, self._h = lib, handle
+
+    @property
+    def info(self):
+        i = LabelMeshInfo()
+        _check(self.lib.fn["labelmesh_info_get"](self._h, C.byref(i)), "labelmesh_info_get")
+        return {"vertices": i.vertices, "triangles": i.triangles, "kept": i.kept, "mixed": i.mixed, "refs": i.refs,
+                "cell": i.cell, "origin": tuple(i.origin), "cells": tuple(i.cells)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.fn["labelmesh_destroy"](self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class _OwnedBuffer:
     """a result buffer handed over by the library (malloc'ed there): exposes it through the array interface and gives
     it back with ratsdf_free_buffer when the last array built on it is collected"""
@@ -421,6 +466,19 @@ class Library:
                               "labelset_info_get": [vp, C.POINTER(LabelSetInfo)], "labelset_destroy": [vp],
                               "score_labels": [vp, vp, sp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
                               "score_labels_device": [vp, vp, sp, vp, vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in SCORE_MESH_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                sp = C.POINTER(ScoreParams)
+                make = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_float, C.POINTER(vp)]
+                f.argtypes = {"labelmesh_create": make, "labelmesh_create_device": make,
+                              "labelmesh_info_get": [vp, C.POINTER(LabelMeshInfo)], "labelmesh_destroy": [vp],
+                              "score_mesh": [vp, vp, sp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
+                              "score_mesh_device": [vp, vp, sp, vp, vp, C.c_int64, vp]}[s]
             self.fn[s] = f
 
         for s in FUSE_SYMBOLS:
@@ -974,6 +1032,60 @@ class Engine:
         _check(self.lib.fn["score_labels_device"](self._h, label_set._h, C.byref(params), ptr[0] or None,
                                                   ptr[1] or None, int(capacity), ptr[2] or None),
                "score_labels_device")
+
+    def label_mesh(self, vertices, labels, triangles, cell=0.0):
+        """a LabelMesh (ratsdf_labelmesh_create, include/ratsdf_score_mesh.h): vertices [n, 3] float32 metres, labels
+        [n] uint8 of LABEL_IGNORE / LABEL_LOW / LABEL_HIGH, triangles [m, 3] int32 vertex indices; a triangle carries
+        the label of its first vertex.  cell: the edge of the search grid's cells, 0 for 8 voxel sizes of this engine.
+        With the three arrays on the device (torch tensors or devmem.DeviceArray: float32 [n, 3], uint8 [n] and
+        int32 [m, 3], contiguous) it is built from them in place."""
+        h = C.c_void_p()
+        if hasattr(vertices, "data_ptr"):
+            n = int(labels.shape[0]) if hasattr(labels, "shape") else int(len(labels))
+            m = int(triangles.shape[0]) if hasattr(triangles, "shape") else int(len(triangles))
+            _check(self.lib.fn["labelmesh_create_device"](self._h, vertices.data_ptr() or None,
+                                                          labels.data_ptr() or None, n, triangles.data_ptr() or None,
+                                                          m, C.c_float(float(cell)), C.byref(h)),
+                   "labelmesh_create_device")
+            return LabelMesh(self.lib, h)
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        if lab.shape[0] != xyz.shape[0]:
+            raise ValueError("one label per vertex")
+        _check(self.lib.fn["labelmesh_create"](self._h, xyz.ctypes.data if len(xyz) else None,
+                                               lab.ctypes.data if len(lab) else None, len(xyz),
+                                               tri.ctypes.data if len(tri) else None, len(tri),
+                                               C.c_float(float(cell)), C.byref(h)), "labelmesh_create")
+        return LabelMesh(self.lib, h)
+
+    def score_mesh(self, label_mesh, tsdf_below=0.1, max_dist=None, p_cutoff=0.5, min_weight=0, per_voxel=False):
+        """the map scored against a LabelMesh (ratsdf_score_mesh): every voxel with |tsdf| < tsdf_below and weight >=
+        min_weight takes the label of its nearest triangle within max_dist (default: 4 cells of the set) and counts
+        by prob > p_cutoff against it.  Returns a LabelScore, with per_voxel also VOXEL_LABEL_DTYPE records (nearest:
+        the triangle's index) in the order of gather_valid_semantic()."""
+        if max_dist is None:
+            max_dist = 4.0 * label_mesh.info["cell"]
+        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
+        rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
+        p, m = C.c_void_p(), C.c_size_t()
+        _check(self.lib.fn["score_mesh"](self._h, label_mesh._h, C.byref(params), rec.ctypes.data,
+                                         C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None),
+               "score_mesh")
+        score = LabelScore(rec)
+        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+
+    def score_mesh_device(self, label_mesh, d_score, d_per_voxel, capacity, d_count, tsdf_below=0.1, max_dist=None,
+                          p_cutoff=0.5, min_weight=0):
+        """score_mesh() into DEVICE buffers, asynchronous on the engine's stream, with the buffers of
+        score_labels_device().  Returns nothing: synchronize() before reading."""
+        if max_dist is None:
+            max_dist = 4.0 * label_mesh.info["cell"]
+        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_score, d_per_voxel, d_count)]
+        _check(self.lib.fn["score_mesh_device"](self._h, label_mesh._h, C.byref(params), ptr[0] or None,
+                                                ptr[1] or None, int(capacity), ptr[2] or None),
+               "score_mesh_device")
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,
