@@ -25,6 +25,7 @@
 #include "kernels_esdf.h"
 #include "kernels_surface.h"
 #include "kernels_surface_mesh.h"
+#include "kernels_cluster_mesh.h"
 #include "kernels_regions.h"
 #include "kernels_score.h"
 #include "kernels_score_mesh.h"
@@ -38,6 +39,7 @@
 #include "../../include/ratsdf_esdf.h"
 #include "../../include/ratsdf_surface.h"
 #include "../../include/ratsdf_surface_mesh.h"
+#include "../../include/ratsdf_cluster_mesh.h"
 #include "../../include/ratsdf_regions.h"
 #include "../../include/ratsdf_score.h"
 #include "../../include/ratsdf_score_mesh.h"
@@ -262,6 +264,7 @@ struct EngineMem {
   Workspace ws_surface;       // ratsdf_surface_points*: surface_layout, per cell of the block grid
   Workspace ws_surface_mesh;  // ratsdf_surface_mesh*: surface_mesh_layout, per cell of the block grid
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
+  Workspace ws_cluster_mesh;  // ratsdf_cluster_mesh*: cluster_mesh_layout, per cell of the block grid
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
   Workspace ws_score;         // ratsdf_score_labels: score_layout, one item
   Workspace ws_score_mesh;    // ratsdf_score_mesh: score_mesh_layout, one item
@@ -2073,6 +2076,7 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "resample.inc" // ratsdf_resample_blocks_device / ratsdf_fuse_map_transformed (include/ratsdf_resample.h)
 #include "coarsen.inc"  // ratsdf_coarsen_blocks_device / ratsdf_fuse_map_coarsened (include/ratsdf_coarsen.h)
 #include "surface_mesh.inc"  // ratsdf_surface_mesh[_device] (include/ratsdf_surface_mesh.h)
+#include "cluster_mesh.inc"  // ratsdf_cluster_mesh[_device] (include/ratsdf_cluster_mesh.h)
 #include "regions.inc"  // ratsdf_regions[_device] (include/ratsdf_regions.h)
 #include "score.inc"    // ratsdf_labelset_* / ratsdf_score_labels[_device] (include/ratsdf_score.h)
 #include "score_mesh.inc"  // ratsdf_labelmesh_* / ratsdf_score_mesh[_device] (include/ratsdf_score_mesh.h)

@@ -91,6 +91,26 @@ inline void surface_mesh_layout(WsCursor& c, size_t n, SurfaceMeshWork* w) {  //
   w->code = c.take_raw<uint16_t>(1024 * n);
 }
 
+// clustered mesh (cluster_mesh.inc), a grid of n block cells, a buffer of its own: clusters per cell | triangles per
+// cell | where each cell's clusters start | where its triangles start (4n B each) | the scan's tile sums | the two totals
+// (words) and the host entry point's two int64 counts, a rounded 32 bytes together | the 64-bit mask of each cell's
+// non-empty clusters (8n B)
+struct ClusterMeshWork {
+  uint32_t *cnt_v, *cnt_t, *pos_v, *pos_t, *tiles, *total;
+  long long* counts;
+  unsigned long long* mask;
+};
+inline void cluster_mesh_layout(WsCursor& c, size_t n, ClusterMeshWork* w) {
+  w->cnt_v = c.take<uint32_t>(4 * n);
+  w->cnt_t = c.take<uint32_t>(4 * n);
+  w->pos_v = c.take<uint32_t>(4 * n);
+  w->pos_t = c.take<uint32_t>(4 * n);
+  w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
+  w->total = c.take_raw<uint32_t>(8);
+  w->counts = c.take_raw<long long>(ws_round(32) - 8);
+  w->mask = c.take<unsigned long long>(8 * n);
+}
+
 // regions, a box of n voxels: seed bytes (n B) | labels (4n B) | root flags, then ranks in place (4n B) | the scan's
 // tile sums | the number of regions (a word) and the host entry point's int64 count, 16 bytes together
 struct RegionsWork {

@@ -53,6 +53,9 @@ struct Api {
   // include/ratsdf_surface_mesh.h: likewise optional (not in the CPU oracle)
   int (*surface_mesh)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_surface_mesh_params*,
                       ratsdf_surface_point**, size_t*, int32_t**, size_t*) = nullptr;
+  // include/ratsdf_cluster_mesh.h: likewise optional (not in the CPU oracle)
+  int (*cluster_mesh)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_cluster_mesh_params*,
+                      ratsdf_surface_point**, size_t*, int32_t**, size_t*) = nullptr;
   // include/ratsdf_regions.h: likewise optional (not in the CPU oracle)
   int (*regions)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_regions_params*, int32_t*,
                  ratsdf_region**, size_t*) = nullptr;
@@ -204,6 +207,12 @@ class TSDFGrid {
   // box's complete cells use, each once, and three indices into them per triangle, wound towards free space.  Returns
   // the status (also kept in last_status()); both vectors are empty unless it is RATSDF_OK.  No reference counterpart.
   int SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
+                  std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
+  // clustered mesh of a box of voxels (include/ratsdf_cluster_mesh.h): SurfaceMesh with its vertices merged per
+  // lattice-aligned cluster of params.factor^3 voxels (one record per non-empty cluster, the mean of its members) and
+  // its triangles re-indexed, the degenerate ones dropped, each once.  Returns the status (also kept in
+  // last_status()); both vectors are empty unless it is RATSDF_OK.  The reference simplifies on the host (Open3D).
+  int ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
                   std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
   // connected regions of a box of voxels (include/ratsdf_regions.h): the voxels that params admits grouped by face
   // adjacency inside the box; *labels (may be nullptr) receives dims[0] * dims[1] * dims[2] labels, *regions the table,

@@ -168,6 +168,9 @@ class TSDFSystem {
   // TSDFGrid::SurfaceMesh under the engine's mutex, like Sample
   int SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
                   std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
+  // TSDFGrid::ClusterMesh under the engine's mutex, like Sample
+  int ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
+                  std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
   // TSDFGrid::Regions under the engine's mutex, like ESDF
   int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
               std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);

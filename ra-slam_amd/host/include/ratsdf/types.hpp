@@ -21,6 +21,7 @@
 #include "../../../../include/ratsdf_esdf.h"
 #include "../../../../include/ratsdf_surface.h"
 #include "../../../../include/ratsdf_surface_mesh.h"
+#include "../../../../include/ratsdf_cluster_mesh.h"
 #include "../../../../include/ratsdf_regions.h"
 #include "../../../../include/ratsdf_score.h"
 #include "../../../../include/ratsdf_score_mesh.h"

@@ -31,6 +31,10 @@
 //          (float), red green blue (uchar), prob (float), weight (uchar); faces as lists of three int indices.  The box
 //          is tiled as for --surface-points; each tile's mesh is self-contained, so the vertices on a face two tiles
 //          share are written once per tile: duplicates there are accepted)]
+//          [--cluster-mesh FILE.ply [--cluster-factor K (2, 4 or 8; default 4)] (after the last frame: the clustered
+//          mesh of the map's bounding box, include/ratsdf_cluster_mesh.h, min_weight 1, in the PLY layout of
+//          --surface-mesh.  ONE box, not tiled: clustered meshes of neighbouring boxes do not stitch, so a bounding box
+//          of more than 1024 voxels along an axis is refused)]
 //          [--score-labels FILE [--score-cutoff P (0.5)] [--score-max-dist D (4 cells of the set)]
 //          [--score-tsdf-below T (0.1)] (after the last frame: the map scored against the labelled points of FILE, raw
 //          16-byte records {float x, y, z; uint32 label} with label 0 unannotated, 1 low-touch, 2 high-touch --
@@ -103,6 +107,39 @@ int write_surface_points(TSDFSystem& tsdf, float vs, const std::string& path) {
   return RATSDF_OK;
 }
 
+// a mesh as a binary little-endian PLY: vertices x y z nx ny nz (float), red green blue (uchar), prob (float), weight
+// (uchar); faces as lists of three int indices
+void write_ply(const std::vector<ratsdf_surface_point>& vertices, const std::vector<int32_t>& triangles,
+               const char* kind, float vs, const std::string& path) {
+  const size_t nv = vertices.size(), nt = triangles.size() / 3;
+  char header[512];
+  const int hn = snprintf(header, sizeof(header),
+                          "ply\nformat binary_little_endian 1.0\ncomment ratsdf %s mesh, voxel size %g\n"
+                          "element vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                          "property float nx\nproperty float ny\nproperty float nz\n"
+                          "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                          "property float prob\nproperty uchar weight\n"
+                          "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
+                          kind, vs, nv, nt);
+  std::vector<uint8_t> file((size_t)hn + nv * 32 + nt * 13);
+  uint8_t* p = file.data();
+  memcpy(p, header, (size_t)hn), p += hn;
+  for (const ratsdf_surface_point& v : vertices) {  // 24 + 3 + 4 + 1 bytes: the record, colour before probability
+    memcpy(p, v.pos, 12), memcpy(p + 12, v.normal, 12);
+    p[24] = v.rgbw.r, p[25] = v.rgbw.g, p[26] = v.rgbw.b;
+    memcpy(p + 27, &v.prob, 4);
+    p[31] = v.rgbw.weight;
+    p += 32;
+  }
+  for (size_t i = 0; i < nt; ++i) {
+    *p = 3;
+    memcpy(p + 1, &triangles[3 * i], 12);
+    p += 13;
+  }
+  write_file(path, file.data(), file.size());
+  fprintf(stderr, "[offline_eval] %zu vertices, %zu triangles to %s\n", nv, nt, path.c_str());
+}
+
 // the welded triangle mesh of the map's bounding box (include/ratsdf_surface_mesh.h) as a binary little-endian PLY;
 // tiled exactly as write_surface_points tiles, each tile's indices offset by the vertices written before it
 int write_surface_mesh(TSDFSystem& tsdf, float vs, const std::string& path) {
@@ -127,33 +164,28 @@ int write_surface_mesh(TSDFSystem& tsdf, float vs, const std::string& path) {
           for (const int32_t i : part_t) triangles.push_back(base + i);
         }
   }
-  const size_t nv = vertices.size(), nt = triangles.size() / 3;
-  char header[512];
-  const int hn = snprintf(header, sizeof(header),
-                          "ply\nformat binary_little_endian 1.0\ncomment ratsdf surface mesh, voxel size %g\n"
-                          "element vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
-                          "property float nx\nproperty float ny\nproperty float nz\n"
-                          "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-                          "property float prob\nproperty uchar weight\n"
-                          "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
-                          vs, nv, nt);
-  std::vector<uint8_t> file((size_t)hn + nv * 32 + nt * 13);
-  uint8_t* p = file.data();
-  memcpy(p, header, (size_t)hn), p += hn;
-  for (const ratsdf_surface_point& v : vertices) {  // 24 + 3 + 4 + 1 bytes: the record, colour before probability
-    memcpy(p, v.pos, 12), memcpy(p + 12, v.normal, 12);
-    p[24] = v.rgbw.r, p[25] = v.rgbw.g, p[26] = v.rgbw.b;
-    memcpy(p + 27, &v.prob, 4);
-    p[31] = v.rgbw.weight;
-    p += 32;
+  write_ply(vertices, triangles, "surface", vs, path);
+  return RATSDF_OK;
+}
+
+// the clustered mesh of the map's bounding box (include/ratsdf_cluster_mesh.h) as a PLY of the same layout.  ONE box:
+// meshes of boxes that tile space do not stitch (a cluster that a box cuts averages only that box's members), so a
+// bounding box beyond the header's limits (1024 voxels along an axis, 2^27 voxels) is refused by the library
+int write_cluster_mesh(TSDFSystem& tsdf, float vs, int factor, const std::string& path) {
+  std::vector<ratsdf_surface_point> vertices;
+  std::vector<int32_t> triangles;
+  int lo[3], hi[3];
+  if (map_bounds(tsdf, vs, lo, hi)) {
+    ratsdf_cluster_mesh_params params;
+    memset(&params, 0, sizeof(params));
+    params.min_weight = 1;
+    params.factor = factor;
+    const int32_t origin[3] = {lo[0], lo[1], lo[2]};
+    const int32_t dims[3] = {hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1};
+    const int st = tsdf.ClusterMesh(origin, dims, params, &vertices, &triangles);
+    if (st != RATSDF_OK) return st;
   }
-  for (size_t i = 0; i < nt; ++i) {
-    *p = 3;
-    memcpy(p + 1, &triangles[3 * i], 12);
-    p += 13;
-  }
-  write_file(path, file.data(), file.size());
-  fprintf(stderr, "[offline_eval] %zu vertices, %zu triangles to %s\n", nv, nt, path.c_str());
+  write_ply(vertices, triangles, "cluster", vs, path);
   return RATSDF_OK;
 }
 
@@ -278,7 +310,8 @@ int main(int argc, char** argv) {
   float voxel_size = 0.01f, max_depth = 6.f;  // offline_eval.cc:49-53
   int device = 0, max_frames = -1, threads = 4, first_frame = 0;
   std::string download_all, download_mesh, dump_dir, load_map, save_map, fuse_map, surface_points, save_coarse_map;
-  std::string surface_mesh, score_file, score_mesh_file;
+  std::string surface_mesh, cluster_mesh, score_file, score_mesh_file;
+  int cluster_factor = 4;
   float score_cutoff = 0.5f, score_max_dist = 0.f, score_tsdf_below = 0.1f;
   int coarse_levels = 1;
   bool reader_only = false, dump_raw_color = false;
@@ -307,6 +340,8 @@ int main(int argc, char** argv) {
     else if (a == "--fuse-map") fuse_map = next();
     else if (a == "--surface-points") surface_points = next();
     else if (a == "--surface-mesh") surface_mesh = next();
+    else if (a == "--cluster-mesh") cluster_mesh = next();
+    else if (a == "--cluster-factor") cluster_factor = atoi(next());
     else if (a == "--score-labels") score_file = next();
     else if (a == "--score-mesh") score_mesh_file = next();
     else if (a == "--score-cutoff") score_cutoff = strtof(next(), nullptr);
@@ -446,6 +481,14 @@ int main(int argc, char** argv) {
         const int st = write_surface_mesh(*tsdf, voxel_size, surface_mesh);
         if (st != RATSDF_OK) {
           fprintf(stderr, "[offline_eval] --surface-mesh %s: %s\n", surface_mesh.c_str(),
+                  Api::Load(lib).status_string(st));
+          return 1;
+        }
+      }
+      if (!cluster_mesh.empty()) {
+        const int st = write_cluster_mesh(*tsdf, voxel_size, cluster_factor, cluster_mesh);
+        if (st != RATSDF_OK) {
+          fprintf(stderr, "[offline_eval] --cluster-mesh %s: %s\n", cluster_mesh.c_str(),
                   Api::Load(lib).status_string(st));
           return 1;
         }

@@ -86,6 +86,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
   api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
   api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
+  api.cluster_mesh = reinterpret_cast<decltype(api.cluster_mesh)>(opt_sym("cluster_mesh"));
   api.regions = reinterpret_cast<decltype(api.regions)>(opt_sym("regions"));
   api.labelset_create = reinterpret_cast<decltype(api.labelset_create)>(opt_sym("labelset_create"));
   api.labelset_info_get = reinterpret_cast<decltype(api.labelset_info_get)>(opt_sym("labelset_info_get"));
@@ -317,6 +318,26 @@ int TSDFGrid::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const 
   note(api_->surface_mesh ? api_->surface_mesh(engine_, origin, dims, &params, &v, &nv, &t, &nt)
                           : RATSDF_ERR_NOT_IMPLEMENTED,
        "SurfaceMesh");
+  if (status_ == RATSDF_OK) {
+    if (v) vertices->assign(v, v + nv);
+    if (t) triangles->assign(t, t + 3 * nt);
+  }
+  if (v) api_->free_buffer(v);
+  if (t) api_->free_buffer(t);
+  return status_;
+}
+
+int TSDFGrid::ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
+                          std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
+  if (vertices) vertices->clear();
+  if (triangles) triangles->clear();
+  if (!engine_ || !vertices || !triangles) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_surface_point* v = nullptr;
+  int32_t* t = nullptr;
+  size_t nv = 0, nt = 0;
+  note(api_->cluster_mesh ? api_->cluster_mesh(engine_, origin, dims, &params, &v, &nv, &t, &nt)
+                          : RATSDF_ERR_NOT_IMPLEMENTED,
+       "ClusterMesh");
   if (status_ == RATSDF_OK) {
     if (v) vertices->assign(v, v + nv);
     if (t) triangles->assign(t, t + 3 * nt);
@@ -744,6 +765,12 @@ int TSDFSystem::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], cons
                             std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.SurfaceMesh(origin, dims, params, vertices, triangles);
+}
+
+int TSDFSystem::ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
+                            std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.ClusterMesh(origin, dims, params, vertices, triangles);
 }
 
 int TSDFSystem::Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,

@@ -13,6 +13,7 @@ from ._abi import (BLOCK_DTYPE, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED, ESDF_STATE
 from ._abi import (LABEL_HIGH, LABEL_IGNORE, LABEL_LOW, LABEL_SCORE_DTYPE, VOXEL_LABEL_DTYPE, LabelScore, LabelSet,
                    ScoreParams)
 from ._abi import LabelMesh, LabelMeshInfo
+from ._abi import ClusterMeshParams
 from .pose import compose, identity_pose, invert, pose_from_matrix
 
 _PKG_ROOT = Path(__file__).resolve().parent.parent
@@ -52,4 +53,5 @@ __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "P
            "RGBW_DTYPE", "SAMPLE_DTYPE", "VOXEL_TSDF_DTYPE", "VOXEL_SEGM_DTYPE", "LIB_PATH", "voxel_box",
            "ESDF_UNKNOWN_OCCUPIED", "ESDF_STATE_UNKNOWN", "ESDF_STATE_FREE", "ESDF_STATE_OCCUPIED",
            "SURFACE_DTYPE", "REGION_DTYPE", "RegionsParams", "LABEL_SCORE_DTYPE", "VOXEL_LABEL_DTYPE", "ScoreParams",
-           "LabelSet", "LabelScore", "LABEL_IGNORE", "LABEL_LOW", "LABEL_HIGH", "LabelMesh", "LabelMeshInfo"]
+           "LabelSet", "LabelScore", "LABEL_IGNORE", "LABEL_LOW", "LABEL_HIGH", "LabelMesh", "LabelMeshInfo",
+           "ClusterMeshParams"]

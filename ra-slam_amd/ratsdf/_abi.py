@@ -125,6 +125,15 @@ class SurfaceMeshParams(C.Structure):
                 ("reserved1", C.c_uint32)]
 
 
+# include/ratsdf_cluster_mesh.h (clustered mesh of a box): handled like SURFACE_MESH_SYMBOLS
+CLUSTER_MESH_SYMBOLS = ["cluster_mesh", "cluster_mesh_device"]
+
+
+class ClusterMeshParams(C.Structure):
+    """ratsdf_cluster_mesh_params"""
+    _fields_ = [("min_weight", C.c_int32), ("factor", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # include/ratsdf_regions.h (connected regions of a box): handled like ESDF_SYMBOLS
 REGIONS_SYMBOLS = ["regions", "regions_device"]
 # ratsdf_region (32 bytes)
@@ -443,6 +452,17 @@ class Library:
                 f.argtypes = box + {"surface_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
                                                      C.POINTER(C.c_size_t)],
                                     "surface_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in CLUSTER_MESH_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(ClusterMeshParams)]
+                f.argtypes = box + {"cluster_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                                     C.POINTER(C.c_size_t)],
+                                    "cluster_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
             self.fn[s] = f
         for s in REGIONS_SYMBOLS:
             f = getattr(self.dll, prefix + s, None)
@@ -938,6 +958,35 @@ class Engine:
                                                   C.byref(params), ptr[0] or None, int(vertex_capacity),
                                                   ptr[1] or None, int(triangle_capacity), ptr[2] or None),
                "surface_mesh_device")
+        self.synchronize()
+        if hasattr(d_counts, "cpu"):         # a torch tensor
+            return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])
+        if hasattr(d_counts, "numpy"):       # a devmem.DeviceArray
+            return tuple(int(v) for v in d_counts.numpy().view(np.int64).reshape(-1)[:2])
+        return None                          # a raw pointer: the caller reads it
+
+    def cluster_mesh(self, origin, dims, factor=4, min_weight=1):
+        """clustered mesh of a box of voxels (ratsdf_cluster_mesh, include/ratsdf_cluster_mesh.h): (vertices,
+        triangles).  surface_mesh() of the same box with its vertices merged per lattice-aligned cluster of factor^3
+        voxels (factor 2, 4 or 8): one SURFACE_DTYPE record per non-empty cluster -- the mean of its members -- in
+        block order, then cluster order within the block; the triangles are int32 [n, 3] indices into them, those with
+        two vertices in one cluster dropped, the smallest index first, each once."""
+        pv, pt, nv, nt = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        params = ClusterMeshParams(int(min_weight), int(factor), 0, 0)
+        _check(self.lib.fn["cluster_mesh"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                           C.byref(pv), C.byref(nv), C.byref(pt), C.byref(nt)), "cluster_mesh")
+        return self._take(pv, nv.value, SURFACE_DTYPE), self._take(pt, nt.value * 3, np.dtype("<i4")).reshape(-1, 3)
+
+    def cluster_mesh_device(self, origin, dims, d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts,
+                            factor=4, min_weight=1):
+        """cluster_mesh() into DEVICE buffers, asynchronous on the engine's stream: the arguments, the capacity rule
+        and the result of surface_mesh_device()."""
+        params = ClusterMeshParams(int(min_weight), int(factor), 0, 0)
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_vertices, d_triangles, d_counts)]
+        _check(self.lib.fn["cluster_mesh_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
+                                                  C.byref(params), ptr[0] or None, int(vertex_capacity),
+                                                  ptr[1] or None, int(triangle_capacity), ptr[2] or None),
+               "cluster_mesh_device")
         self.synchronize()
         if hasattr(d_counts, "cpu"):         # a torch tensor
             return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])

@@ -3,7 +3,8 @@
 the CPU oracle (16 threads): tools/aux_bench.py  (GPU box).  The last leg times the surface points
 (include/ratsdf_surface.h) and the welded surface mesh (include/ratsdf_surface_mesh.h) beside the mesh export and the
 host route on the same map; `--surface` runs that leg and the mesh export alone (no oracle); `--no-oracle` runs every row on the HIP engine alone (a same-box A/B of two
-libraries, RATSDF_LIB, needs no CPU column)."""
+libraries, RATSDF_LIB, needs no CPU column); `--cluster` runs the `--surface` legs and then times the clustered mesh
+(include/ratsdf_cluster_mesh.h) at k = 2, 4, 8 beside the welded mesh, both over the bounding box as ONE box."""
 import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -17,7 +18,7 @@ from oracle_binding import load_oracle
 
 vs, md = 0.005, 4.0
 gpu = ratsdf.TSDFGrid(vs, 6 * vs)
-only_surface = "--surface" in sys.argv
+only_surface = "--surface" in sys.argv or "--cluster" in sys.argv
 cpu = None if only_surface or "--no-oracle" in sys.argv else Engine(load_oracle(), vs, 6 * vs, threads=16)
 frames = [synthetic.frame("room", i, noise=True, holes=True) for i in range(45)]
 for f in frames:
@@ -116,3 +117,24 @@ try:
 except ratsdf.RatsdfError as err:
     if err.status != 6:
         raise
+
+# ---- the clustered mesh of the bounding box as one box, k = 2, 4, 8, beside the welded mesh of the same box ----
+if "--cluster" in sys.argv:
+    box = ([int(v) for v in lo], [int(v) for v in hi - lo + 1])
+    assert max(box[1]) <= 1024 and np.prod(box[1], dtype=np.int64) <= 1 << 27, box
+    d_cnt2 = devmem.DeviceArray(np.zeros(2, dtype=np.int64))
+    nv, nt = gpu.surface_mesh_device(*box, 0, 0, 0, 0, d_cnt2)
+    d_v = devmem.DeviceArray(np.zeros((nv + 1, 8), dtype=np.int32))
+    d_t = devmem.DeviceArray(np.zeros((nt + 1, 3), dtype=np.int32))
+    t_w, _ = timed(lambda: gpu.surface_mesh_device(*box, d_v, nv, d_t, nt, d_cnt2), 20)
+    t_wc, _ = timed(lambda: gpu.surface_mesh_device(*box, 0, 0, 0, 0, d_cnt2), 20)
+    print(f"cluster mesh: one box {box[1]} voxels at {box[0]}")
+    print(f"  surface_mesh_device                   {t_w * 1e3:8.2f} ms   ({nv} vertices, {nt} triangles; "
+          f"pure count {t_wc * 1e3:.2f} ms)")
+    for k in (2, 4, 8):
+        cv, ct = gpu.cluster_mesh_device(*box, 0, 0, 0, 0, d_cnt2, k)
+        t_c, got = timed(lambda: gpu.cluster_mesh_device(*box, d_v, cv, d_t, ct, d_cnt2, k), 20)
+        t_cc, _ = timed(lambda: gpu.cluster_mesh_device(*box, 0, 0, 0, 0, d_cnt2, k), 20)
+        assert got == (cv, ct)
+        print(f"  cluster_mesh_device, k = {k}            {t_c * 1e3:8.2f} ms   ({cv} vertices, {ct} triangles; "
+              f"pure count {t_cc * 1e3:.2f} ms; {t_c / t_w:.2f} x the welded mesh)")
