@@ -27,6 +27,7 @@
 #include "kernels_surface_mesh.h"
 #include "kernels_cluster_mesh.h"
 #include "kernels_regions.h"
+#include "kernels_cost.h"
 #include "kernels_score.h"
 #include "kernels_score_mesh.h"
 #include "kernels_fuse.h"
@@ -41,6 +42,7 @@
 #include "../../include/ratsdf_surface_mesh.h"
 #include "../../include/ratsdf_cluster_mesh.h"
 #include "../../include/ratsdf_regions.h"
+#include "../../include/ratsdf_cost.h"
 #include "../../include/ratsdf_score.h"
 #include "../../include/ratsdf_score_mesh.h"
 
@@ -266,6 +268,7 @@ struct EngineMem {
   DevMem d_surface_mesh_tab;  // ... and its case tables, built on first use
   Workspace ws_cluster_mesh;  // ratsdf_cluster_mesh*: cluster_mesh_layout, per cell of the block grid
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
+  Workspace ws_cost;          // ratsdf_cost_to_go*: cost_layout, per voxel (an ESDF workspace of its own inside)
   Workspace ws_score;         // ratsdf_score_labels: score_layout, one item
   Workspace ws_score_mesh;    // ratsdf_score_mesh: score_mesh_layout, one item
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
@@ -2078,5 +2081,6 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "surface_mesh.inc"  // ratsdf_surface_mesh[_device] (include/ratsdf_surface_mesh.h)
 #include "cluster_mesh.inc"  // ratsdf_cluster_mesh[_device] (include/ratsdf_cluster_mesh.h)
 #include "regions.inc"  // ratsdf_regions[_device] (include/ratsdf_regions.h)
+#include "cost.inc"     // ratsdf_cost_to_go[_device] (include/ratsdf_cost.h)
 #include "score.inc"    // ratsdf_labelset_* / ratsdf_score_labels[_device] (include/ratsdf_score.h)
 #include "score_mesh.inc"  // ratsdf_labelmesh_* / ratsdf_score_mesh[_device] (include/ratsdf_score_mesh.h)

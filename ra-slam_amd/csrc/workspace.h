@@ -1,4 +1,4 @@
-// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc), score.inc and score_mesh.inc carve their device
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc, cost.inc), score.inc and score_mesh.inc carve their device
 // workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
 // struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
 // written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
@@ -126,6 +126,26 @@ inline void regions_layout(WsCursor& c, size_t n, RegionsWork* w) {  // (offsets
   w->tiles = c.take<uint32_t>(4 * scan_tiles(n));
   w->total = c.take_raw<uint32_t>(8);
   w->count = c.take_raw<long long>(8);
+}
+
+// cost to go (cost.inc), a box of n voxels, a buffer of its own: an ESDF workspace of its own (esdf_layout, from the
+// same cursor: state and field of the box) | traversable bytes (n B) | the dirty flags of the tiles, two arrays by round
+// parity (4 B a tile each) | the host entry point's summary (32 B), then the two dirty counts: a rounded 256 bytes.
+// cost_tiles_max(n): no box of n voxels has more 32 x 8 x 4 tiles -- ceil(X/32) ceil(Y/8) ceil(Z/4) <=
+// (X/32 + 1)(Y/8 + 1)(Z/4 + 1) <= n (1 + 4 + 8 + 32) / 1024 + 1024 (1/32 + 1/8 + 1/4) + 1, every axis being <= 1024
+// and every product of two axes <= n.
+inline size_t cost_tiles_max(size_t n) { return n / 16 + 420; }
+struct CostWork {
+  EsdfWork esdf;
+  uint8_t* trav;
+  uint32_t *dirty, *summary, *counts;
+};
+inline void cost_layout(WsCursor& c, size_t n, CostWork* w) {
+  esdf_layout(c, n, &w->esdf);
+  w->trav = c.take<uint8_t>(n);
+  w->dirty = c.take<uint32_t>(8 * cost_tiles_max(n));
+  w->summary = c.take_raw<uint32_t>(32);
+  w->counts = c.take_raw<uint32_t>(ws_round(40) - 32);
 }
 
 // label score (score.inc), n = 1: the score table of the host entry point (520 int64) | its int64 count, 16 bytes

@@ -59,6 +59,9 @@ struct Api {
   // include/ratsdf_regions.h: likewise optional (not in the CPU oracle)
   int (*regions)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_regions_params*, int32_t*,
                  ratsdf_region**, size_t*) = nullptr;
+  // include/ratsdf_cost.h: likewise optional (not in the CPU oracle)
+  int (*cost_to_go)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_cost_params*, const int32_t*, int32_t,
+                    uint32_t*, uint8_t*, ratsdf_cost_summary*) = nullptr;
   // include/ratsdf_score.h: likewise optional (not in the CPU oracle)
   int (*labelset_create)(ratsdf_engine*, const float*, const uint8_t*, size_t, float, ratsdf_labelset**) = nullptr;
   int (*labelset_info_get)(const ratsdf_labelset*, ratsdf_labelset_info*) = nullptr;
@@ -220,6 +223,14 @@ class TSDFGrid {
   // No reference counterpart.
   int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
               std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);
+  // cost-to-go field of a box of voxels (include/ratsdf_cost.h): the least chamfer length of a path through
+  // traversable voxels from every voxel to one of the n_goals goals (absolute voxel triples); *cost receives dims[0] *
+  // dims[1] * dims[2] words, *next (may be nullptr) as many direction bytes, *summary (may be nullptr) the summary.
+  // params.rounds must be 0: the call runs to convergence.  Returns the status (also kept in last_status()); both
+  // vectors are empty unless it is RATSDF_OK.  No reference counterpart.
+  int CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params, const int32_t* goals,
+               int32_t n_goals, std::vector<uint32_t>* cost, std::vector<uint8_t>* next,
+               ratsdf_cost_summary* summary);
   // the map scored against labelled points (include/ratsdf_score.h).  MakeLabelSet: n points (xyz: 3 floats each,
   // metres) with a label each (RATSDF_LABEL_*) into *out (what it held is destroyed first); cell: the edge of the
   // search grid, 0 for 8 voxel sizes.  ScoreLabels: every voxel that params selects takes the label of its nearest

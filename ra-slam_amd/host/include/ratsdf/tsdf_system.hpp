@@ -174,6 +174,10 @@ class TSDFSystem {
   // TSDFGrid::Regions under the engine's mutex, like ESDF
   int Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
               std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions);
+  // TSDFGrid::CostToGo under the engine's mutex, like ESDF
+  int CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params, const int32_t* goals,
+               int32_t n_goals, std::vector<uint32_t>* cost, std::vector<uint8_t>* next,
+               ratsdf_cost_summary* summary);
   // TSDFGrid::MakeLabelSet / TSDFGrid::ScoreLabels under the engine's mutex, like ESDF
   int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
   int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,

@@ -23,6 +23,7 @@
 #include "../../../../include/ratsdf_surface_mesh.h"
 #include "../../../../include/ratsdf_cluster_mesh.h"
 #include "../../../../include/ratsdf_regions.h"
+#include "../../../../include/ratsdf_cost.h"
 #include "../../../../include/ratsdf_score.h"
 #include "../../../../include/ratsdf_score_mesh.h"
 

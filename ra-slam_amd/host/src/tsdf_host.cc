@@ -88,6 +88,7 @@ const Api& Api::Load(const char* path, const char* prefix) {
   api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
   api.cluster_mesh = reinterpret_cast<decltype(api.cluster_mesh)>(opt_sym("cluster_mesh"));
   api.regions = reinterpret_cast<decltype(api.regions)>(opt_sym("regions"));
+  api.cost_to_go = reinterpret_cast<decltype(api.cost_to_go)>(opt_sym("cost_to_go"));
   api.labelset_create = reinterpret_cast<decltype(api.labelset_create)>(opt_sym("labelset_create"));
   api.labelset_info_get = reinterpret_cast<decltype(api.labelset_info_get)>(opt_sym("labelset_info_get"));
   api.labelset_destroy = reinterpret_cast<decltype(api.labelset_destroy)>(opt_sym("labelset_destroy"));
@@ -368,6 +369,32 @@ int TSDFGrid::Regions(const int32_t origin[3], const int32_t dims[3], const rats
     labels->clear();
   }
   if (r) api_->free_buffer(r);
+  return status_;
+}
+
+int TSDFGrid::CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params,
+                       const int32_t* goals, int32_t n_goals, std::vector<uint32_t>* cost, std::vector<uint8_t>* next,
+                       ratsdf_cost_summary* summary) {
+  if (cost) cost->clear();
+  if (next) next->clear();
+  if (!engine_ || !cost) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  size_t n = 1;  // (a box beyond the header's limits gets a one-voxel placeholder: the library refuses it)
+  for (int a = 0; dims && a < 3; ++a) n = dims[a] >= 1 && dims[a] <= 1024 && n ? n * (size_t)dims[a] : 0;
+  n = dims && n && n <= ((size_t)1 << 27) ? n : 1;
+  cost->resize(n);
+  if (next) next->resize(n);
+  ratsdf_cost_summary s;
+  memset(&s, 0, sizeof(s));
+  note(api_->cost_to_go ? api_->cost_to_go(engine_, origin, dims, &params, goals, n_goals, cost->data(),
+                                           next ? next->data() : nullptr, &s)
+                        : RATSDF_ERR_NOT_IMPLEMENTED,
+       "CostToGo");
+  if (status_ != RATSDF_OK) {
+    cost->clear();
+    if (next) next->clear();
+  } else if (summary) {
+    *summary = s;
+  }
   return status_;
 }
 
@@ -777,6 +804,13 @@ int TSDFSystem::Regions(const int32_t origin[3], const int32_t dims[3], const ra
                         std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   return tsdf_.Regions(origin, dims, params, labels, regions);
+}
+
+int TSDFSystem::CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params,
+                         const int32_t* goals, int32_t n_goals, std::vector<uint32_t>* cost,
+                         std::vector<uint8_t>* next, ratsdf_cost_summary* summary) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.CostToGo(origin, dims, params, goals, n_goals, cost, next, summary);
 }
 
 int TSDFSystem::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {

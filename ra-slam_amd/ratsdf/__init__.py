@@ -14,6 +14,8 @@ from ._abi import (LABEL_HIGH, LABEL_IGNORE, LABEL_LOW, LABEL_SCORE_DTYPE, VOXEL
                    ScoreParams)
 from ._abi import LabelMesh, LabelMeshInfo
 from ._abi import ClusterMeshParams
+from ._abi import (COST_AT_GOAL, COST_CONTINUE, COST_FACES_ONLY, COST_NO_STEP, COST_NONE, COST_SUMMARY_DTYPE,
+                   COST_THROUGH_UNKNOWN, COST_UNKNOWN_OCCUPIED, CostParams, cost_direction, descend)
 from .pose import compose, identity_pose, invert, pose_from_matrix
 
 _PKG_ROOT = Path(__file__).resolve().parent.parent
@@ -54,4 +56,6 @@ __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "P
            "ESDF_UNKNOWN_OCCUPIED", "ESDF_STATE_UNKNOWN", "ESDF_STATE_FREE", "ESDF_STATE_OCCUPIED",
            "SURFACE_DTYPE", "REGION_DTYPE", "RegionsParams", "LABEL_SCORE_DTYPE", "VOXEL_LABEL_DTYPE", "ScoreParams",
            "LabelSet", "LabelScore", "LABEL_IGNORE", "LABEL_LOW", "LABEL_HIGH", "LabelMesh", "LabelMeshInfo",
-           "ClusterMeshParams"]
+           "ClusterMeshParams", "CostParams", "COST_SUMMARY_DTYPE", "COST_NONE", "COST_AT_GOAL", "COST_NO_STEP",
+           "COST_UNKNOWN_OCCUPIED", "COST_THROUGH_UNKNOWN", "COST_FACES_ONLY", "COST_CONTINUE",
+           "cost_direction", "descend"]

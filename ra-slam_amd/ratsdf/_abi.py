@@ -147,6 +147,28 @@ class RegionsParams(C.Structure):
     _fields_ = [("occupied_below", C.c_float), ("min_prob", C.c_float), ("states", C.c_uint32), ("flags", C.c_uint32)]
 
 
+# include/ratsdf_cost.h (cost-to-go field of a box): handled like ESDF_SYMBOLS
+COST_SYMBOLS = ["cost_to_go", "cost_to_go_device"]
+COST_UNKNOWN_OCCUPIED, COST_THROUGH_UNKNOWN, COST_FACES_ONLY, COST_CONTINUE = 1, 2, 4, 8
+COST_NONE = 0xFFFFFFFF
+COST_AT_GOAL, COST_NO_STEP = 255, 254       # `next` bytes that are no direction code
+# ratsdf_cost_summary (32 bytes)
+COST_SUMMARY_DTYPE = np.dtype([("goals", "<i4"), ("traversable", "<i4"), ("reached", "<i4"), ("max_cost", "<u4"),
+                               ("pending", "<i4"), ("rounds", "<i4"), ("reserved", "<u4", (2,))])
+assert COST_SUMMARY_DTYPE.itemsize == 32
+
+
+def cost_direction(code):
+    """(dx, dy, dz) of a direction code (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1)"""
+    code = int(code)
+    return code % 3 - 1, code // 3 % 3 - 1, code // 9 - 1
+
+
+class CostParams(C.Structure):
+    """ratsdf_cost_params"""
+    _fields_ = [("occupied_below", C.c_float), ("clearance", C.c_float), ("flags", C.c_uint32), ("rounds", C.c_int32)]
+
+
 # include/ratsdf_score.h (label sets and the map's score against them): handled like ESDF_SYMBOLS
 SCORE_SYMBOLS = ["labelset_create", "labelset_create_device", "labelset_info_get", "labelset_destroy", "score_labels",
                  "score_labels_device"]
@@ -324,6 +346,30 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
 
 
+def descend(next, origin, start, max_steps=None):
+    """follows the direction bytes `next` (shape (Z, Y, X), of a box at `origin`) from the absolute voxel `start`:
+    the voxel path as an int32 [k, 3] array, start first.  It ends at a COST_AT_GOAL voxel, at a COST_NO_STEP voxel
+    (the path is then just what led there), after max_steps moves (default: the box's voxels), or where a move would
+    leave the box."""
+    nxt = np.asarray(next)
+    Z, Y, X = nxt.shape
+    v = [int(a) - int(b) for a, b in zip(start, origin)]
+    if not (0 <= v[0] < X and 0 <= v[1] < Y and 0 <= v[2] < Z):
+        raise ValueError("start outside the box")
+    limit = nxt.size if max_steps is None else int(max_steps)
+    path = [tuple(v)]
+    for _ in range(limit):
+        code = int(nxt[v[2], v[1], v[0]])
+        if code >= 27:
+            break
+        dx, dy, dz = cost_direction(code)
+        v = [v[0] + dx, v[1] + dy, v[2] + dz]
+        if not (0 <= v[0] < X and 0 <= v[1] < Y and 0 <= v[2] < Z):
+            break
+        path.append(tuple(v))
+    return (np.asarray(path, dtype=np.int64) + np.asarray(origin, dtype=np.int64)).astype(np.int32).reshape(-1, 3)
+
+
 class Library:
     """A loaded shared library exporting the ABI under ``prefix``."""
 
@@ -473,6 +519,15 @@ class Library:
                 box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(RegionsParams)]
                 f.argtypes = box + {"regions": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
                                     "regions_device": [vp, vp, C.c_int64, vp]}[s]
+            self.fn[s] = f
+        for s in COST_SYMBOLS:
+            f = getattr(self.dll, prefix + s, None)
+            if f is None:
+                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+            else:
+                f.restype = C.c_int
+                f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(CostParams), vp, C.c_int32,
+                              vp, vp, vp]
             self.fn[s] = f
         for s in SCORE_SYMBOLS:
             f = getattr(self.dll, prefix + s, None)
@@ -1029,6 +1084,57 @@ class Engine:
             return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
         if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
             return int(d_count.numpy().view(np.int64).reshape(-1)[0])
+        return None                          # a raw pointer: the caller reads it
+
+    @staticmethod
+    def _cost_flags(unknown_occupied, through_unknown, faces_only, resume=False):
+        return ((COST_UNKNOWN_OCCUPIED if unknown_occupied else 0) | (COST_THROUGH_UNKNOWN if through_unknown else 0) |
+                (COST_FACES_ONLY if faces_only else 0) | (COST_CONTINUE if resume else 0))
+
+    def cost_to_go(self, origin, dims, goals, clearance=0.0, occupied_below=0.0, unknown_occupied=False,
+                   through_unknown=False, faces_only=False, with_next=False):
+        """cost-to-go field of a box of voxels (ratsdf_cost_to_go, include/ratsdf_cost.h): for every traversable voxel
+        -- FREE (or UNKNOWN with through_unknown), outside the ESDF's obstacle set and not closer to it than `clearance`
+        metres -- the least chamfer length (10 / 14 / 17 a face / edge / corner move; faces_only: face moves only) of a
+        path through traversable voxels to one of `goals` ([n, 3] absolute voxel indices; those outside the box or not
+        traversable are ignored).  Returns (cost, [next,] summary): cost uint32 of shape (dims[2], dims[1], dims[0]),
+        COST_NONE where no goal is reached; with with_next the uint8 direction codes (COST_AT_GOAL, COST_NO_STEP or
+        (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1): see descend()); summary a COST_SUMMARY_DTYPE record."""
+        o, d = _box3(origin, "origin"), _box3(dims, "dims")
+        n = int(np.prod([int(v) for v in d], dtype=object))
+        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
+        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 3))
+        cost = np.empty(shape, dtype=np.uint32)
+        nxt = np.empty(shape, dtype=np.uint8) if with_next else None
+        summary = np.zeros(1, dtype=COST_SUMMARY_DTYPE)
+        params = CostParams(float(occupied_below), float(clearance),
+                            self._cost_flags(unknown_occupied, through_unknown, faces_only), 0)
+        _check(self.lib.fn["cost_to_go"](self._h, o, d, C.byref(params), g.ctypes.data if len(g) else None, len(g),
+                                         cost.ctypes.data, nxt.ctypes.data if with_next else None,
+                                         summary.ctypes.data), "cost_to_go")
+        return (cost, nxt, summary[0]) if with_next else (cost, summary[0])
+
+    def cost_to_go_device(self, origin, dims, d_goals, n_goals, d_cost, d_next, d_summary, rounds, clearance=0.0,
+                          occupied_below=0.0, unknown_occupied=False, through_unknown=False, faces_only=False,
+                          resume=False):
+        """cost_to_go() into DEVICE buffers, asynchronous on the engine's stream, with exactly `rounds` (1 .. 4096)
+        relaxation rounds: the goals from d_goals (n_goals int32 triples, 16-byte aligned), the cost words to d_cost
+        (16-byte aligned), the direction bytes to d_next (0 for none) and the 32-byte summary to d_summary (8-byte
+        aligned).  summary["pending"] != 0: not converged yet -- the field is an upper bound that `next` still
+        descends to a goal; call again with resume=True and the same arguments to go on from it.  Each buffer: a torch
+        tensor, a devmem.DeviceArray or a raw pointer.  Returns the summary record (this waits for the stream)."""
+        params = CostParams(float(occupied_below), float(clearance),
+                            self._cost_flags(unknown_occupied, through_unknown, faces_only, resume), int(rounds))
+        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_goals, d_cost, d_next, d_summary)]
+        _check(self.lib.fn["cost_to_go_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                                ptr[0] or None, int(n_goals), ptr[1] or None, ptr[2] or None,
+                                                ptr[3] or None), "cost_to_go_device")
+        self.synchronize()
+        if hasattr(d_summary, "cpu"):        # a torch tensor
+            return d_summary.cpu().numpy().reshape(-1).view(np.uint8)[:32].view(COST_SUMMARY_DTYPE)[0]
+        if hasattr(d_summary, "numpy"):      # a devmem.DeviceArray
+            return d_summary.numpy().reshape(-1).view(np.uint8)[:32].view(COST_SUMMARY_DTYPE)[0]
         return None                          # a raw pointer: the caller reads it
 
     def label_set(self, points, labels, cell=0.0):
