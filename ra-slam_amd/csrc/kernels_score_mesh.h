@@ -2,9 +2,10 @@
 // the build of a mesh set (bounds and validation -> references per cell -> scan -> scatter into a dense grid of cells)
 // and the join "every selected voxel -> its nearest kept triangle" with the counts that follow from it.
 //
-// The join walks the selection list of k_score_labels, one 256-thread workgroup per map block at a time, and the same
-// rings of cells around the block (kernels_score.h): a cell references every kept triangle whose axis-aligned box meets
-// it, each ring's references are resolved to 48-byte triangle records and staged in LDS in chunks of kMeshChunk.
+// The join walks the selection list of k_score_labels, one 256-thread workgroup per map block at a time, and the rings
+// of cells around the block with the same function (score_walk, kernels_score.h): a cell references every kept triangle
+// whose axis-aligned box meets it, each ring's references are resolved to 48-byte triangle records and staged in LDS in
+// chunks of kMeshChunk.
 // A pair (voxel, triangle) costs about ten times a pair (voxel, point), and only a few percent of a block's voxels are
 // selected, so the workgroup first compacts its selected voxels (a block scan of the two flags per thread) and spreads
 // the product (S selected voxels) x (staged triangles) over its lanes: with S <= 256, lane l works for voxel l % S on
@@ -16,11 +17,11 @@
 // staged more than once, which a minimum does not notice.  -DRATSDF_SCORE_MESH_PLAIN builds the other layout for the
 // A/B of DESIGN 4 "Label score against a mesh": no compaction, two voxels per lane as in k_score_labels.
 //
-// The grid only accelerates.  The closest point q of a triangle is clamped to the triangle's box, so dist2 is at least
-// the squared distance from the voxel to that box along any axis, up to the rounding of one subtraction and one
-// product (2^-22 relative).  After ring r every triangle that has not been looked at has its box, along some axis, at
-// least r whole cells beyond the block's extent (up to cell * 2^-28 of double rounding, as for points), so the point
-// score's bound (r * cell * (1 - 1e-5))^2, rounded down, ends the walk with the same margin.
+// The grid only accelerates, and score_walk's argument for where the walk may stop holds with a triangle's box in the
+// place of a point: the closest point q of a triangle is clamped to the triangle's box, so dist2 is at least the
+// squared distance from the voxel to that box along any axis, up to the rounding of one subtraction and one product
+// (2^-22 relative, a point's margin), and a triangle that has not been looked at after ring r has its box, along some
+// axis, at least r whole cells beyond the block's extent.
 #pragma once
 #include "kernels_score.h"
 
@@ -31,17 +32,18 @@ namespace ratsdf {
 #endif
 constexpr int kMeshChunk = RATSDF_SCORE_MESH_CHUNK;  // 48-byte triangle records per LDS chunk (256: 12 KiB)
 constexpr int kMeshLanes = 8;                        // lanes that share the cells of one triangle's box in the build
-constexpr int kMeshMaxRing = 192;                    // never reached with max_dist <= 64 * cell: a guard, not a contract
 constexpr unsigned long long kMeshNoKey = ~0ull;
+#ifdef RATSDF_SCORE_MESH_PLAIN
+constexpr bool kMeshPlain = true;
+#else
+constexpr bool kMeshPlain = false;
+#endif
 
 // the device side of a mesh set, by value
-struct MeshGrid {
+struct MeshGrid : CellGrid {
   const float4* rec;      // three per ORIGINAL triangle index, written for kept ones: {a, index bits}, {b, 0}, {c, 0}
-  const uint32_t* start;  // cells + 1 words: where each cell's references start
   const uint32_t* ref;    // original indices of kept triangles, sorted by cell
   const uint8_t* label;   // one byte per original triangle index: the label of its first vertex
-  double ox, oy, oz, cell;
-  int cx, cy, cz;
 };
 
 // Triangle t of the caller's arrays: 0 -- an index outside [0, nv) (nothing is loaded through it), 1 -- dropped
@@ -246,25 +248,9 @@ __device__ __forceinline__ void mesh_take(float d2, uint32_t idx, float md2, uns
   if (d2 <= md2 && k < best) best = k;
 }
 
-// one voxel's place in the counts (LDS, laid out like ratsdf_label_score) and its per-voxel record
-__device__ __forceinline__ int2 mesh_voxel(bool selected, unsigned long long key, float prob, const uint8_t* tlabel,
-                                           const ScoreArgs& a, uint32_t* cnt) {
-  if (!selected) return make_int2(-1, 0x7FC00000);
-  atomicAdd(&cnt[1], 1u);
-  if (key == kMeshNoKey) {
-    atomicAdd(&cnt[2], 1u);
-    return make_int2(-2, 0x7FC00000);
-  }
-  const uint32_t label = tlabel[(uint32_t)key];
-  if (label == 0u) {
-    atomicAdd(&cnt[3], 1u);
-  } else {
-    const bool high = label == 2u, pred = prob > a.p_cutoff;
-    atomicAdd(&cnt[4 + (pred ? (high ? 0 : 1) : (high ? 2 : 3))], 1u);
-    const int bin = prob >= 1.0f ? 255 : prob > 0.0f ? (int)(prob * 256.0f) : 0;
-    atomicAdd(&cnt[8 + (high ? 256 : 0) + bin], 1u);
-  }
-  return make_int2((int)(uint32_t)key, (int)(uint32_t)(key >> 32));
+// the dist2 that the voxel of key k has still to beat (score_walk's best): its own, md2 while it has no match
+__device__ __forceinline__ float mesh_to_beat(unsigned long long k, float md2) {
+  return k != kMeshNoKey ? __uint_as_float((uint32_t)(k >> 32)) : md2;
 }
 
 // Blocks b = blockIdx.x, blockIdx.x + gridDim.x, ... of the selection list (the order of k_download: per-voxel record
@@ -277,9 +263,6 @@ __global__ __launch_bounds__(kScoreWG) void k_score_mesh(Pool pool, const VisIte
   __shared__ uint32_t seg_start[2 * kScoreWG], seg_off[2 * kScoreWG];
   __shared__ uint32_t scan_lds[32];
   __shared__ uint32_t cnt[kScoreWords];
-#ifndef RATSDF_SCORE_MESH_PLAIN
-  __shared__ uint16_t list[2 * kScoreWG];  // the block's selected voxels
-#endif
   const int tid = threadIdx.x;
   const uint32_t n = *n_sel;
   for (int i = tid; i < kScoreWords; i += kScoreWG) cnt[i] = 0u;
@@ -300,12 +283,12 @@ __global__ __launch_bounds__(kScoreWG) void k_score_mesh(Pool pool, const VisIte
     // the voxels this lane works for (v0, v1: -1 for none), on the triangles part, part + parts, ... of a chunk
     int v0 = -1, v1 = -1;
     uint32_t part = 0, parts = 1, S = 0;
-#ifdef RATSDF_SCORE_MESH_PLAIN
-    S = (uint32_t)__syncthreads_or(sel0 || sel1);
-    v0 = sel0 ? tid : -1;
-    v1 = sel1 ? tid + kScoreWG : -1;
-#else
-    {
+    if (kMeshPlain) {
+      S = (uint32_t)__syncthreads_or(sel0 || sel1);
+      v0 = sel0 ? tid : -1;
+      v1 = sel1 ? tid + kScoreWG : -1;
+    } else {
+      __shared__ uint16_t list[2 * kScoreWG];  // the block's selected voxels
       const uint32_t at = block_exclusive_scan((uint32_t)sel0 + (uint32_t)sel1, scan_lds, &S);
       if (sel0) list[at] = (uint16_t)tid;
       if (sel1) list[at + (uint32_t)sel0] = (uint16_t)(tid + kScoreWG);
@@ -321,110 +304,51 @@ __global__ __launch_bounds__(kScoreWG) void k_score_mesh(Pool pool, const VisIte
         }
       }
     }
-#endif
     const float q0x = (float)(g0x + (v0 & 7)) * vs, q0y = (float)(g0y + ((v0 >> 3) & 7)) * vs,
                 q0z = (float)(g0z + ((v0 >> 6) & 7)) * vs;
     const float q1x = (float)(g0x + (v1 & 7)) * vs, q1y = (float)(g0y + ((v1 >> 3) & 7)) * vs,
                 q1z = (float)(g0z + ((v1 >> 6) & 7)) * vs;
     unsigned long long k0 = kMeshNoKey, k1 = kMeshNoKey;
-    if (S) {  // uniform
-      // the cells the block's extent reaches, per axis (not clamped to the grid)
-      const int lox = score_cell_open((float)g0x * vs, g.ox, g.cell),
-                hix = score_cell_open((float)(g0x + 7) * vs, g.ox, g.cell);
-      const int loy = score_cell_open((float)g0y * vs, g.oy, g.cell),
-                hiy = score_cell_open((float)(g0y + 7) * vs, g.oy, g.cell);
-      const int loz = score_cell_open((float)g0z * vs, g.oz, g.cell),
-                hiz = score_cell_open((float)(g0z + 7) * vs, g.oz, g.cell);
-      for (int r = 0;; ++r) {  // uniform
-        // the cube of radius r and the one before it, clipped to the grid
-        const int X0 = max(lox - r, 0), X1 = min(hix + r, g.cx - 1), Y0 = max(loy - r, 0), Y1 = min(hiy + r, g.cy - 1),
-                  Z0 = max(loz - r, 0), Z1 = min(hiz + r, g.cz - 1);
-        const int iX0 = max(lox - r + 1, 0), iX1 = min(hix + r - 1, g.cx - 1), iY0 = max(loy - r + 1, 0),
-                  iY1 = min(hiy + r - 1, g.cy - 1), iZ0 = max(loz - r + 1, 0), iZ1 = min(hiz + r - 1, g.cz - 1);
-        if (X0 <= X1 && Y0 <= Y1 && Z0 <= Z1) {
-          const int ny = Y1 - Y0 + 1, nrows = ny * (Z1 - Z0 + 1);
-          for (int row0 = 0; row0 < nrows; row0 += kScoreWG) {  // uniform: a row of cells per thread
-            uint32_t s0 = 0, c0 = 0, s1 = 0, c1 = 0;
-            const int i = row0 + tid;
-            if (i < nrows) {
-              const int y = Y0 + i % ny, z = Z0 + i / ny;
-              const uint32_t base = (uint32_t)((z * g.cy + y) * g.cx);
-              int a0 = X0, a1 = X1, b0 = 1, b1 = 0;  // the row's new cells: [a0, a1] and [b0, b1]
-              if (r > 0 && y >= iY0 && y <= iY1 && z >= iZ0 && z <= iZ1) {
-                a1 = min(iX0 - 1, X1);
-                b0 = max(iX1 + 1, X0);
-                b1 = X1;
+    if (S)  // uniform
+      score_walk<kMeshChunk>(
+          g, g0x, g0y, g0z, vs, seg_start, seg_off, scan_lds,
+          [&](uint32_t pos, uint32_t j) {
+            const size_t t = g.ref[pos];
+            recs[3 * j] = g.rec[3 * t];
+            recs[3 * j + 1] = g.rec[3 * t + 1];
+            recs[3 * j + 2] = g.rec[3 * t + 2];
+          },
+          [&](uint32_t m) {
+            if (v0 >= 0) {
+              for (uint32_t j = part; j < m; j += parts) {
+                const float4 A = recs[3 * j], B = recs[3 * j + 1], C = recs[3 * j + 2];
+                const uint32_t idx = __float_as_uint(A.w);
+                mesh_take(mesh_dist2(q0x, q0y, q0z, A, B, C), idx, a.md2, k0);
+                if (v1 >= 0) mesh_take(mesh_dist2(q1x, q1y, q1z, A, B, C), idx, a.md2, k1);
               }
-              if (a0 <= a1) {
-                s0 = g.start[base + a0];
-                c0 = g.start[base + a1 + 1] - s0;
-              }
-              if (b0 <= b1) {
-                s1 = g.start[base + b0];
-                c1 = g.start[base + b1 + 1] - s1;
+            } else if (kMeshPlain && v1 >= 0) {  // (only that layout has lanes that hold a second voxel alone)
+              for (uint32_t j = 0; j < m; ++j) {
+                const float4 A = recs[3 * j], B = recs[3 * j + 1], C = recs[3 * j + 2];
+                mesh_take(mesh_dist2(q1x, q1y, q1z, A, B, C), __float_as_uint(A.w), a.md2, k1);
               }
             }
-            uint32_t total = 0;
-            // (its two barriers stand between the last chunk's readers of the run tables and the writes below)
-            const uint32_t ex = block_exclusive_scan(c0 + c1, scan_lds, &total);
-            seg_start[2 * tid] = s0;
-            seg_start[2 * tid + 1] = s1;
-            seg_off[2 * tid] = ex;
-            seg_off[2 * tid + 1] = ex + c0;
-            __syncthreads();
-            for (uint32_t k = 0; k < total; k += kMeshChunk) {  // uniform
-              const uint32_t m = min((uint32_t)kMeshChunk, total - k);
-              for (uint32_t j = tid; j < m; j += kScoreWG) {
-                const uint32_t pos = k + j;
-                uint32_t lo = 0, hi = 2 * kScoreWG;  // the last segment that starts at or before pos
-                while (hi - lo > 1) {
-                  const uint32_t mid = (lo + hi) >> 1;
-                  if (seg_off[mid] <= pos) lo = mid; else hi = mid;
-                }
-                const size_t t = g.ref[seg_start[lo] + (pos - seg_off[lo])];
-                recs[3 * j] = g.rec[3 * t];
-                recs[3 * j + 1] = g.rec[3 * t + 1];
-                recs[3 * j + 2] = g.rec[3 * t + 2];
-              }
+          },
+          [&] {
+            if (parts > 1) {  // uniform: the lanes of a voxel meet
+              if (v0 >= 0 && k0 != kMeshNoKey) atomicMin(&key[v0], k0);
               __syncthreads();
-              if (v0 >= 0) {
-                for (uint32_t j = part; j < m; j += parts) {
-                  const float4 A = recs[3 * j], B = recs[3 * j + 1], C = recs[3 * j + 2];
-                  const uint32_t idx = __float_as_uint(A.w);
-                  mesh_take(mesh_dist2(q0x, q0y, q0z, A, B, C), idx, a.md2, k0);
-                  if (v1 >= 0) mesh_take(mesh_dist2(q1x, q1y, q1z, A, B, C), idx, a.md2, k1);
-                }
-              }
-#ifdef RATSDF_SCORE_MESH_PLAIN
-              else if (v1 >= 0) {
-                for (uint32_t j = 0; j < m; ++j) {
-                  const float4 A = recs[3 * j], B = recs[3 * j + 1], C = recs[3 * j + 2];
-                  mesh_take(mesh_dist2(q1x, q1y, q1z, A, B, C), __float_as_uint(A.w), a.md2, k1);
-                }
-              }
-#endif
-              __syncthreads();
+              if (v0 >= 0) k0 = key[v0];
             }
-          }
-        }
-        if (parts > 1) {  // uniform: the lanes of a voxel meet
-          if (v0 >= 0 && k0 != kMeshNoKey) atomicMin(&key[v0], k0);
-          __syncthreads();
-          if (v0 >= 0) k0 = key[v0];
-        }
-        const double reach = (double)r * g.cell * (1.0 - 1e-5);
-        const float bound = __double2float_rd(reach * reach);
-        const bool done = (v0 < 0 || (k0 != kMeshNoKey ? __uint_as_float((uint32_t)(k0 >> 32)) : a.md2) < bound) &&
-                          (v1 < 0 || (k1 != kMeshNoKey ? __uint_as_float((uint32_t)(k1 >> 32)) : a.md2) < bound);
-        const bool whole = X0 == 0 && Y0 == 0 && Z0 == 0 && X1 == g.cx - 1 && Y1 == g.cy - 1 && Z1 == g.cz - 1;
-        if (__syncthreads_and(done) || whole || r >= kMeshMaxRing) break;
-      }
-    }
+            return fmaxf(v0 >= 0 ? mesh_to_beat(k0, a.md2) : -1.f, v1 >= 0 ? mesh_to_beat(k1, a.md2) : -1.f);
+          });
     if (v0 >= 0 && k0 != kMeshNoKey) atomicMin(&key[v0], k0);
     if (v1 >= 0 && k1 != kMeshNoKey) atomicMin(&key[v1], k1);
     __syncthreads();
-    const int2 r0 = mesh_voxel(sel0, key[tid], pool.segm[vi], g.label, a, cnt);
-    const int2 r1 = mesh_voxel(sel1, key[tid + kScoreWG], pool.segm[vi + 256], g.label, a, cnt);
+    const unsigned long long e0 = key[tid], e1 = key[tid + kScoreWG];
+    const int2 r0 = score_voxel(sel0, e0 != kMeshNoKey, (int)(uint32_t)e0, (uint32_t)(e0 >> 32), pool.segm[vi],
+                                g.label, a, cnt);
+    const int2 r1 = score_voxel(sel1, e1 != kMeshNoKey, (int)(uint32_t)e1, (uint32_t)(e1 >> 32), pool.segm[vi + 256],
+                                g.label, a, cnt);
     const long long o = (long long)b * 512 + tid;
     if (per_voxel) {
       if (o < capacity) per_voxel[o] = r0;

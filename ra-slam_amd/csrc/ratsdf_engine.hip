@@ -269,8 +269,7 @@ struct EngineMem {
   Workspace ws_cluster_mesh;  // ratsdf_cluster_mesh*: cluster_mesh_layout, per cell of the block grid
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
   Workspace ws_cost;          // ratsdf_cost_to_go*: cost_layout, per voxel (an ESDF workspace of its own inside)
-  Workspace ws_score;         // ratsdf_score_labels: score_layout, one item
-  Workspace ws_score_mesh;    // ratsdf_score_mesh: score_mesh_layout, one item
+  Workspace ws_score;         // ratsdf_score_labels and ratsdf_score_mesh: score_layout, one item
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use

@@ -1,6 +1,7 @@
 // score_mesh.inc -- the map scored against a labelled triangle mesh (include/ratsdf_score_mesh.h): mesh sets and the
-// host side of kernels_score_mesh.h.  Included at the end of ratsdf_engine.hip, after score.inc (it shares score_args'
-// checks of the parameters and the grid of workgroups).
+// host side of kernels_score_mesh.h.  Included at the end of ratsdf_engine.hip, after score.inc, which holds what the
+// two kinds of set share: the helpers of the builds, the parameter check, the launch and the bodies of the scoring
+// entry points.
 
 static_assert(sizeof(ratsdf_labelmesh_info) == 72 && offsetof(ratsdf_labelmesh_info, refs) == 32 &&
                   offsetof(ratsdf_labelmesh_info, cell) == 40 && offsetof(ratsdf_labelmesh_info, cells) == 56,
@@ -28,8 +29,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
   std::unique_ptr<ratsdf_labelmesh> s(new (std::nothrow) ratsdf_labelmesh);
   if (!s) return RATSDF_ERR_DEVICE;
   s->device = e->device;
-  float c = cell == 0.f ? 8.f * e->vs : cell;
-  while (c < 1e-6f) c *= 2.f;
+  float c = score_cell_edge(e, cell);
   struct {
     uint32_t lo[3], hi[3], bad_label, bad_index, kept, mixed, total, pad, refs[2], pad2[2];
   } hb;
@@ -56,23 +56,13 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
   double lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0}, cells[3] = {1, 1, 1};
   unsigned long long refs = 0;
   if (kept) {
-    for (int a = 0; a < 3; ++a) {
-      const uint32_t bl = score_unord(hb.lo[a]), bh = score_unord(hb.hi[a]);
-      float fl, fh;
-      memcpy(&fl, &bl, 4);
-      memcpy(&fh, &bh, 4);
-      lo[a] = (double)(fl + 0.f);  // (-0.0 is reported as 0.0)
-      ext[a] = (double)fh - (double)fl;
-    }
-    g.ox = lo[0], g.oy = lo[1], g.oz = lo[2];
+    score_bounds(hb.lo, hb.hi, lo, ext);
     unsigned long long* const d_refs = (unsigned long long*)(d_bounds.as<uint32_t>() + 12);
     for (;; c *= 2.f) {
       if (!std::isfinite(c)) return RATSDF_ERR_BAD_ARGUMENT;
-      for (int a = 0; a < 3; ++a) cells[a] = std::floor(ext[a] / (double)c) + 1.0;
-      if (cells[0] * cells[1] * cells[2] > kLabelMaxCells) continue;
+      if (!score_cells(ext, c, cells)) continue;
       // the references of this edge: a sum of products of spans, no pass over cells
-      g.cell = (double)c;
-      g.cx = (int)cells[0], g.cy = (int)cells[1], g.cz = (int)cells[2];
+      score_grid(s.get(), lo, c, cells);
       HIPCHK(hipMemsetAsync(d_refs, 0, 8, e->stream));
       hipLaunchKernelGGL(k_mesh_refs, dim3(tgrid), dim3(256), 0, e->stream, d_xyz, nv, d_tri, nt, g, d_refs);
       HIPCHK(hipGetLastError());
@@ -83,8 +73,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
   const size_t ncell = (size_t)cells[0] * (size_t)cells[1] * (size_t)cells[2];
   STCHK(s->start.alloc(4 * (ncell + 1)));
   HIPCHK(hipMemsetAsync(s->start.as<void>(), 0, 4 * (ncell + 1), e->stream));
-  g.ox = lo[0], g.oy = lo[1], g.oz = lo[2], g.cell = (double)c;
-  g.cx = (int)cells[0], g.cy = (int)cells[1], g.cz = (int)cells[2];
+  score_grid(s.get(), lo, c, cells);
   g.start = s->start.as<const uint32_t>();
   if (kept) {
     STCHK(s->rec.alloc(48 * nt));
@@ -116,33 +105,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
   s->info.kept = (int64_t)kept;
   s->info.mixed = (int64_t)hb.mixed;
   s->info.refs = (int64_t)refs;
-  s->info.cell = c;
-  for (int a = 0; a < 3; ++a) {
-    s->info.origin[a] = (float)lo[a];
-    s->info.cells[a] = (int32_t)cells[a];
-  }
   *out = s.release();
-  return RATSDF_OK;
-}
-
-// argument checks of both scoring entry points (RATSDF_ERR_BAD_ARGUMENT when false): score_args' for a mesh set
-static bool score_mesh_args(const ratsdf_engine* e, const ratsdf_labelmesh* s, const ratsdf_score_params* p) {
-  if (!s || !p || s->device != e->device) return false;
-  const float md2 = p->max_dist * p->max_dist;
-  return !std::isnan(p->tsdf_below) && !std::isnan(p->p_cutoff) && std::isfinite(p->max_dist) && p->max_dist > 0.f &&
-         p->max_dist <= 64.f * s->info.cell && std::isfinite(md2) && md2 > 0.f && p->min_weight <= 255u &&
-         p->flags == 0u && p->reserved[0] == 0u && p->reserved[1] == 0u && p->reserved[2] == 0u;
-}
-
-// the join over the blocks that e->select has listed: the score at d_score, the per-voxel records (if any) at d_pv
-static int score_mesh_launch(ratsdf_engine* e, const ratsdf_labelmesh* s, const ratsdf_score_params& p, void* d_score,
-                             void* d_pv, int64_t capacity, void* d_count) {
-  HIPCHK(hipMemsetAsync(d_score, 0, sizeof(ratsdf_label_score), e->stream));
-  const ScoreArgs a = {p.tsdf_below, p.max_dist * p.max_dist, p.p_cutoff, p.min_weight};
-  hipLaunchKernelGGL(k_score_mesh, dim3(kScoreGrid), dim3(kScoreWG), 0, e->stream, e->pool, (const VisItem*)e->vis,
-                     (const uint32_t*)&e->ctl->n_sel, e->vs, s->grid, a, (unsigned long long*)d_score, (int2*)d_pv,
-                     (long long)capacity, (long long*)d_count);
-  HIPCHK(hipGetLastError());
   return RATSDF_OK;
 }
 
@@ -178,64 +141,18 @@ int ratsdf_labelmesh_create(ratsdf_engine* e, const float* xyz, const uint8_t* l
                          d_tri.as<const int32_t>(), n_triangles, cell, out);
 }
 
-int ratsdf_labelmesh_info_get(const ratsdf_labelmesh* m, ratsdf_labelmesh_info* out) {
-  if (!m || !out) return RATSDF_ERR_BAD_ARGUMENT;
-  *out = m->info;
-  return RATSDF_OK;
-}
+int ratsdf_labelmesh_info_get(const ratsdf_labelmesh* m, ratsdf_labelmesh_info* out) { return set_info_get(m, out); }
 
-// (waits for the device first: a scoring call queued on any engine's stream may still read the set)
-int ratsdf_labelmesh_destroy(ratsdf_labelmesh* m) {
-  if (!m) return RATSDF_ERR_BAD_ARGUMENT;
-  DeviceGuard guard(m->device);
-  if (!guard.ok()) return RATSDF_ERR_DEVICE;
-  const hipError_t err = hipDeviceSynchronize();
-  delete m;
-  return err == hipSuccess ? RATSDF_OK : RATSDF_ERR_DEVICE;
-}
+int ratsdf_labelmesh_destroy(ratsdf_labelmesh* m) { return set_destroy(m); }
 
 int ratsdf_score_mesh_device(ratsdf_engine* e, const ratsdf_labelmesh* m, const ratsdf_score_params* p, void* d_score,
                              void* d_per_voxel, int64_t capacity, void* d_count) {
-  ENTRY(e, capacity >= 0 && d_score && !((uintptr_t)d_score & 7u) && !((uintptr_t)d_per_voxel & 7u) && d_count &&
-               !((uintptr_t)d_count & 7u) && score_mesh_args(e, m, p));
-  STCHK(box_entry(e));
-  STCHK(e->select(kSelValid, GridBounds{}, &e->ctl->n_sel));
-  return score_mesh_launch(e, m, *p, d_score, d_per_voxel, capacity, d_count);
+  return score_device(e, k_score_mesh, m, p, d_score, d_per_voxel, capacity, d_count);
 }
 
 int ratsdf_score_mesh(ratsdf_engine* e, const ratsdf_labelmesh* m, const ratsdf_score_params* p,
                       ratsdf_label_score* out, ratsdf_voxel_label** per_voxel, size_t* n_out) {
-  ENTRY(e, out && (!per_voxel || n_out) && score_mesh_args(e, m, p));
-  STCHK(box_entry(e));
-  ScoreMeshWork w;
-  STCHK(e->workspace(e->ws_score_mesh, 1, score_mesh_layout, &w));
-  STCHK(e->staging(0, kHostChunk));
-  STCHK(e->select(kSelValid, GridBounds{}, &e->ctl->n_sel));
-  uint32_t nb = 0;
-  STCHK(e->read_small(&nb, &e->ctl->n_sel, 4));
-  STCHK(sticky_raised(e));
-  const size_t total = per_voxel ? (size_t)nb * RATSDF_BLOCK_VOLUME : 0;
-  if (total) {
-    const HostPart part = {total, sizeof(ratsdf_voxel_label), (void**)per_voxel, n_out};
-    STCHK(hand_over(e, &part, 1, [&](uint8_t* const* d) {
-      return score_mesh_launch(e, m, *p, w.score, d[0], (int64_t)total, w.count);
-    }));
-  } else {
-    if (per_voxel) *per_voxel = nullptr, *n_out = 0;
-    STCHK(score_mesh_launch(e, m, *p, w.score, nullptr, 0, w.count));
-  }
-  ratsdf_label_score host;
-  int st = e->download(&host, w.score, sizeof(host));
-  if (st == RATSDF_OK) st = e->sticky();
-  if (st != RATSDF_OK) {
-    if (per_voxel && *per_voxel) {
-      free(*per_voxel);
-      *per_voxel = nullptr, *n_out = 0;
-    }
-    return st;
-  }
-  *out = host;
-  return RATSDF_OK;
+  return score_host(e, k_score_mesh, m, p, out, per_voxel, n_out);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc, cost.inc), score.inc and score_mesh.inc carve their device
-// workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc, cost.inc) and the label
+// scores (score.inc) carve their device workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
 // struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
 // written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
 // compiles it alone.  ratsdf_engine::workspace (ratsdf_engine.hip) owns the buffers and their grow step.
@@ -148,21 +148,12 @@ inline void cost_layout(WsCursor& c, size_t n, CostWork* w) {
   w->counts = c.take_raw<uint32_t>(ws_round(40) - 32);
 }
 
-// label score (score.inc), n = 1: the score table of the host entry point (520 int64) | its int64 count, 16 bytes
+// label score against points and against a mesh (score_host in score.inc serves both, from one buffer), n = 1: the
+// score table of the host entry point (520 int64) | its int64 count, 16 bytes
 struct ScoreWork {
   long long *score, *count;
 };
 inline void score_layout(WsCursor& c, size_t n, ScoreWork* w) {
-  w->score = c.take<long long>(4160 * n);
-  w->count = c.take_raw<long long>(16);
-}
-
-// label score against a mesh (score_mesh.inc), n = 1: as score_layout, a buffer of its own -- the score table of the
-// host entry point (520 int64) | its int64 count, 16 bytes
-struct ScoreMeshWork {
-  long long *score, *count;
-};
-inline void score_mesh_layout(WsCursor& c, size_t n, ScoreMeshWork* w) {
   w->score = c.take<long long>(4160 * n);
   w->count = c.take_raw<long long>(16);
 }

@@ -192,22 +192,24 @@ class LabelSetInfo(C.Structure):
                 ("cells", C.c_int32 * 3), ("reserved", C.c_uint32)]
 
 
-class LabelSet:
-    """labelled points on the device (ratsdf_labelset): built by Engine.label_set, immutable, usable by every engine of
-    the same device until close()"""
+class _LabelHandle:
+    """a set of labelled records on the device, LabelSet or LabelMesh: the handle, its info and its release.  A
+    subclass names the symbols' prefix, the info struct and the fields of it that `info` reports."""
+    _prefix, _Info, _fields = None, None, ()
 
     def __init__(self, lib, handle):
         self.lib, self._h = lib, handle
 
     @property
     def info(self):
-        i = LabelSetInfo()
-        _check(self.lib.fn["labelset_info_get"](self._h, C.byref(i)), "labelset_info_get")
-        return {"points": i.points, "kept": i.kept, "cell": i.cell, "origin": tuple(i.origin), "cells": tuple(i.cells)}
+        i = self._Info()
+        _check(self.lib.fn[self._prefix + "_info_get"](self._h, C.byref(i)), self._prefix + "_info_get")
+        values = ((f, getattr(i, f)) for f in self._fields)
+        return {f: tuple(v) if isinstance(v, C.Array) else v for f, v in values}
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.fn["labelset_destroy"](self._h)
+            self.lib.fn[self._prefix + "_destroy"](self._h)
             self._h = None
 
     def __del__(self):
@@ -221,6 +223,12 @@ class LabelSet:
 
     def __exit__(self, *a):
         self.close()
+
+
+class LabelSet(_LabelHandle):
+    """labelled points on the device (ratsdf_labelset): built by Engine.label_set, immutable, usable by every engine of
+    the same device until close()"""
+    _prefix, _Info, _fields = "labelset", LabelSetInfo, ("points", "kept", "cell", "origin", "cells")
 
 
 class LabelScore:
@@ -293,36 +301,11 @@ class LabelMeshInfo(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
-class LabelMesh:
+class LabelMesh(_LabelHandle):
     """a labelled triangle mesh on the device (ratsdf_labelmesh): built by Engine.label_mesh, immutable, usable by
     every engine of the same device until close()"""
-
-    def __init__(self, lib, handle):
-        self.lib, self._h = lib, handle
-
-    @property
-    def info(self):
-        i = LabelMeshInfo()
-        _check(self.lib.fn["labelmesh_info_get"](self._h, C.byref(i)), "labelmesh_info_get")
-        return {"vertices": i.vertices, "triangles": i.triangles, "kept": i.kept, "mixed": i.mixed, "refs": i.refs,
-                "cell": i.cell, "origin": tuple(i.origin), "cells": tuple(i.cells)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.fn["labelmesh_destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    _prefix, _Info = "labelmesh", LabelMeshInfo
+    _fields = ("vertices", "triangles", "kept", "mixed", "refs", "cell", "origin", "cells")
 
 
 class _OwnedBuffer:
@@ -1163,16 +1146,7 @@ class Engine:
         min_weight takes the label of its nearest point within max_dist (default: 4 cells of the set) and counts by
         prob > p_cutoff against it.  Returns a LabelScore, with per_voxel also VOXEL_LABEL_DTYPE records in the order
         of gather_valid_semantic()."""
-        if max_dist is None:
-            max_dist = 4.0 * label_set.info["cell"]
-        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
-        rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
-        p, m = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["score_labels"](self._h, label_set._h, C.byref(params), rec.ctypes.data,
-                                           C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None),
-               "score_labels")
-        score = LabelScore(rec)
-        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+        return self._score("score_labels", label_set, tsdf_below, max_dist, p_cutoff, min_weight, per_voxel)
 
     def score_labels_device(self, label_set, d_score, d_per_voxel, capacity, d_count, tsdf_below=0.1, max_dist=None,
                             p_cutoff=0.5, min_weight=0):
@@ -1180,13 +1154,30 @@ class Engine:
         most `capacity` 8-byte per-voxel records to d_per_voxel (0 for none) and the number of voxels as an int64 to
         d_count; all 8-byte aligned.  Each buffer: a torch tensor, a devmem.DeviceArray or a raw pointer.  Returns
         nothing: synchronize() before reading."""
+        self._score_device("score_labels_device", label_set, d_score, d_per_voxel, capacity, d_count, tsdf_below,
+                           max_dist, p_cutoff, min_weight)
+
+    def _score(self, symbol, labelled, tsdf_below, max_dist, p_cutoff, min_weight, per_voxel):
+        """score_labels() and score_mesh(): `symbol` against the LabelSet or LabelMesh `labelled`"""
         if max_dist is None:
-            max_dist = 4.0 * label_set.info["cell"]
+            max_dist = 4.0 * labelled.info["cell"]
+        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
+        rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
+        p, m = C.c_void_p(), C.c_size_t()
+        _check(self.lib.fn[symbol](self._h, labelled._h, C.byref(params), rec.ctypes.data,
+                                   C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None), symbol)
+        score = LabelScore(rec)
+        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+
+    def _score_device(self, symbol, labelled, d_score, d_per_voxel, capacity, d_count, tsdf_below, max_dist, p_cutoff,
+                      min_weight):
+        """score_labels_device() and score_mesh_device(): `symbol` against the LabelSet or LabelMesh `labelled`"""
+        if max_dist is None:
+            max_dist = 4.0 * labelled.info["cell"]
         params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
         ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_score, d_per_voxel, d_count)]
-        _check(self.lib.fn["score_labels_device"](self._h, label_set._h, C.byref(params), ptr[0] or None,
-                                                  ptr[1] or None, int(capacity), ptr[2] or None),
-               "score_labels_device")
+        _check(self.lib.fn[symbol](self._h, labelled._h, C.byref(params), ptr[0] or None, ptr[1] or None,
+                                   int(capacity), ptr[2] or None), symbol)
 
     def label_mesh(self, vertices, labels, triangles, cell=0.0):
         """a LabelMesh (ratsdf_labelmesh_create, include/ratsdf_score_mesh.h): vertices [n, 3] float32 metres, labels
@@ -1219,28 +1210,14 @@ class Engine:
         min_weight takes the label of its nearest triangle within max_dist (default: 4 cells of the set) and counts
         by prob > p_cutoff against it.  Returns a LabelScore, with per_voxel also VOXEL_LABEL_DTYPE records (nearest:
         the triangle's index) in the order of gather_valid_semantic()."""
-        if max_dist is None:
-            max_dist = 4.0 * label_mesh.info["cell"]
-        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
-        rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
-        p, m = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["score_mesh"](self._h, label_mesh._h, C.byref(params), rec.ctypes.data,
-                                         C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None),
-               "score_mesh")
-        score = LabelScore(rec)
-        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+        return self._score("score_mesh", label_mesh, tsdf_below, max_dist, p_cutoff, min_weight, per_voxel)
 
     def score_mesh_device(self, label_mesh, d_score, d_per_voxel, capacity, d_count, tsdf_below=0.1, max_dist=None,
                           p_cutoff=0.5, min_weight=0):
         """score_mesh() into DEVICE buffers, asynchronous on the engine's stream, with the buffers of
         score_labels_device().  Returns nothing: synchronize() before reading."""
-        if max_dist is None:
-            max_dist = 4.0 * label_mesh.info["cell"]
-        params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_score, d_per_voxel, d_count)]
-        _check(self.lib.fn["score_mesh_device"](self._h, label_mesh._h, C.byref(params), ptr[0] or None,
-                                                ptr[1] or None, int(capacity), ptr[2] or None),
-               "score_mesh_device")
+        self._score_device("score_mesh_device", label_mesh, d_score, d_per_voxel, capacity, d_count, tsdf_below,
+                           max_dist, p_cutoff, min_weight)
 
     def gather_valid_mesh(self):
         """TSDFGrid::GatherValidMesh (voxel_tsdf.cu:736-845): (vertices [n,3] f32 metres,

@@ -1,5 +1,6 @@
-// The workspace layout of the label score (score_layout, ra-slam_amd/csrc/workspace.h), on the host alone: the score
-// table of the host entry point (520 int64, a ratsdf_label_score) and its int64 count behind it.
+// The workspace layout of the label scores, against points and against a mesh (score_layout, ra-slam_amd/csrc/
+// workspace.h: one layout and one buffer for both host entry points), on the host alone: the score table of the host
+// entry point (520 int64, a ratsdf_label_score) and its int64 count behind it.
 //   * the size from a null-based cursor == where the cursor ends on a real base
 //   * the table starts the buffer, holds 4160 bytes per item and is followed by the count on an 8-byte boundary
 //   * the count's 16 bytes end the buffer

@@ -69,6 +69,7 @@ def around(rng, blocks, vs, per_block, spread=1.5):
 
 
 PARAMS = dict(tsdf_below=0.1, max_dist=0.3, p_cutoff=0.5, min_weight=0)
+WIDE_RING_POINTS = np.array([(-8, -8, -8), (16, 16, 16), (3.5, 3.5, 12.5)])   # of "wide_ring", in voxel sizes
 
 
 def _p(**kw):
@@ -121,6 +122,11 @@ def cases():
     add("huge", craft([(0, 0, 0)], tsdf=sparse_tsdf([(0, 0, 0)])), SMALL, VS,
         np.concatenate([near_pts, [(-1e30, 0, 0), (0, 2e30, 0), (3e38, -3e38, 3e38)]]),
         np.concatenate([near_lab, [HIGH, LOW, LOW]]), params=_p(max_dist=0.5))
+    # a ring of more than 256 rows of cells, which the walk takes in two passes: cells of one voxel size, two far
+    # points that stretch the grid 8 and 9 cells beyond the block, and the one point within reach (6 cells) 5.5 cells
+    # above the block's top plane.  The top voxels under it first meet it in ring 5 (18 x 18 rows), in the last slab.
+    add("wide_ring", craft([(0, 0, 0)], tsdf=F(0.03125), weight=1), SMALL, VS64, WIDE_RING_POINTS * VS64,
+        [LOW, IGNORE, HIGH], cell=VS64, params=_p(max_dist=6 * VS64))
 
     # ---- set shape --------------------------------------------------------------------------------------------------
     blk = craft([(0, 0, 0), (1, 0, 0), (0, 1, 1)], tsdf=sparse_tsdf([(0, 0, 0), (1, 0, 0), (0, 1, 1)], 2))
@@ -171,7 +177,7 @@ def case(name):
     return next(c for c in cases() if c.name == name)
 
 
-NAMES = ("ties", "max_dist_edge", "cell_border", "negative", "far", "huge", "one_cell", "doubled_cell", "crowded_2049",
+NAMES = ("ties", "max_dist_edge", "cell_border", "negative", "far", "huge", "wide_ring", "one_cell", "doubled_cell", "crowded_2049",
          "crowded_4097", "points_0", "points_1", "points_255", "points_256", "points_257", "non_finite", "none_finite",
          "selection", "score", "layout_tiny_table", "layout_known_order", "layout_edges")
 
@@ -196,6 +202,30 @@ def expected_info(points, cell, vs):
         info.update(origin=tuple(float(v) + 0.0 for v in lo), cells=tuple(int(v) for v in cells))
     info["cell"] = float(c)
     return info
+
+
+def ring_row(info, pos, vs, lo, hi=None):
+    """where the device's walk (score_walk, kernels_score.h) first meets a record of the set described by `info`
+    (expected_info) whose box is lo .. hi (a point: lo alone), from the block at `pos`: (the ring r, the smallest index
+    among the rows of cells of ring r's cube that hold a cell of the record).  A workgroup takes 256 rows at a time."""
+    o = np.array([float(F(x)) for x in info["origin"]])
+    cell, n = float(F(info["cell"])), np.array(info["cells"])
+    g0 = qc.wrap16(np.asarray(pos, dtype=np.int64) << 3)
+    blo = np.floor(((g0.astype(F) * F(vs)).astype(np.float64) - o) / cell).astype(np.int64)
+    bhi = np.floor((((g0 + 7).astype(F) * F(vs)).astype(np.float64) - o) / cell).astype(np.int64)
+    lo = np.asarray(lo, dtype=F)
+    hi = lo if hi is None else np.asarray(hi, dtype=F)
+    clo = np.clip(np.floor((lo.astype(np.float64) - o) / cell).astype(np.int64), 0, n - 1)
+    chi = np.clip(np.floor((hi.astype(np.float64) - o) / cell).astype(np.int64), 0, n - 1)
+    met = []
+    for x in range(clo[0], chi[0] + 1):
+        for y in range(clo[1], chi[1] + 1):
+            for z in range(clo[2], chi[2] + 1):
+                c = np.array([x, y, z])
+                r = int(max(0, (blo - c).max(), (c - bhi).max()))
+                y0, y1, z0 = max(blo[1] - r, 0), min(bhi[1] + r, n[1] - 1), max(blo[2] - r, 0)
+                met.append((r, int((z - z0) * (y1 - y0 + 1) + (y - y0))))
+    return min(met)
 
 
 def rows_in_order(c, directory_blocks):

@@ -150,6 +150,9 @@ def cases():
     add("far", craft(three, tsdf=sparse_tsdf(three)), SMALL, VS,
         join(near_mesh, small_tris([(-5000.0, 0.1, 0.1), (0.1, 0.1, 900.0)], [HIGH, LOW], 0.5)),
         params=_p(max_dist=0.5))
+    # score_cases' ring of more than 256 rows of cells, its three points as triangles a quarter of a cell wide
+    b = sc.case("wide_ring")
+    add("wide_ring", b.blocks, SMALL, VS64, small_tris(b.points, b.labels, VS64 / 4), cell=VS64, params=b.params)
 
     # ---- dropped --------------------------------------------------------------------------------------------------
     blk3 = [(0, 0, 0), (1, 0, 0), (0, 1, 1)]
@@ -238,7 +241,7 @@ def case(name):
 
 
 NAMES = ("voronoi", "ties", "mixed_labels", "mesh_against_points", "max_dist_edge", "covering_box", "spanning",
-         "cell_border", "negative", "far", "non_finite", "coincident", "unused_vertices", "all_dropped", "no_vertices",
+         "cell_border", "negative", "far", "wide_ring", "non_finite", "coincident", "unused_vertices", "all_dropped", "no_vertices",
          "collinear", "slivers", "tiny", "huge", "tris_0", "tris_1", "tris_255", "tris_256", "tris_257", "crowded_300",
          "crowded_600", "ref_cap", "selection", "score", "layout_tiny_table", "layout_known_order", "layout_edges")
 

@@ -47,6 +47,16 @@ def test_cases_reach_what_they_are_for():
         assert not np.isin(pv["nearest"], np.arange(len(c.points) - 2, len(c.points))).any()
     rec, pv = sc.expected(sc.case("far"), np.arange(3))
     assert (pv["nearest"][512:] < 0).all() and (pv["nearest"][512:] == -2).any()   # the far blocks: nothing matched
+    # the winner of "wide_ring" is first met in the second pass over its ring's rows of cells (256 rows per pass)
+    c = sc.case("wide_ring")
+    rec, pv = sc.expected(c, np.arange(1))
+    matched = pv["nearest"] >= 0
+    assert 0 < matched.sum() < 512 and int(rec["selected"]) == 512 and int(rec["unmatched"]) == 512 - matched.sum()
+    assert set(pv["nearest"][matched]) == {2} and np.flatnonzero(matched).min() >= 7 * 64      # the top plane alone
+    info = sc.expected_info(c.points, c.cell, c.vs)
+    assert info["cell"] == c.vs and min(info["cells"]) == 25
+    ring, row = sc.ring_row(info, c.blocks.pos[0], c.vs, c.points[2])
+    assert ring == 5 and 256 <= row < 18 * 18
     for name in ("points_0", "none_finite"):
         c = sc.case(name)
         rec, _ = sc.expected(c, np.arange(len(c.blocks)))

@@ -5,6 +5,7 @@ are named after, and the float32 contract picks the winners a float64 evaluation
 import numpy as np
 import pytest
 
+import score_cases as sc
 import score_mesh_cases as mc
 import score_mesh_ref as mr
 import score_ref
@@ -99,6 +100,17 @@ def test_cases_reach_what_they_are_for():
         assert (pv["nearest"] == last).any() == (name == "huge")
     rec, pv = mc.expected(mc.case("far"), np.arange(3))
     assert (pv["nearest"][512:] < 0).all() and (pv["nearest"][512:] == -2).any()   # the far blocks: nothing matched
+    # the winner of "wide_ring" is first met in the second pass over its ring's rows of cells (256 rows per pass)
+    c = mc.case("wide_ring")
+    rec, pv = mc.expected(c, np.arange(1))
+    matched = pv["nearest"] >= 0
+    assert 0 < matched.sum() < 512 and int(rec["selected"]) == 512 and int(rec["unmatched"]) == 512 - matched.sum()
+    assert set(pv["nearest"][matched]) == {2} and np.flatnonzero(matched).min() >= 7 * 64      # the top plane alone
+    info = mc.expected_info(c)
+    assert info["cell"] == c.vs and min(info["cells"]) == 25 and info["refs"] == info["kept"] == 3
+    corners = c.vertices[c.triangles[2]]
+    ring, row = sc.ring_row(info, c.blocks.pos[0], c.vs, corners.min(axis=0), corners.max(axis=0))
+    assert ring == 5 and 256 <= row < 18 * 18
     for name in ("tris_0", "all_dropped", "no_vertices"):
         c = mc.case(name)
         rec, _ = mc.expected(c, np.arange(len(c.blocks)))

@@ -1,4 +1,4 @@
-"""The workspace layout of the label score (score_layout in ra-slam_amd/csrc/workspace.h;
+"""The workspace layout of the label scores, points and mesh (score_layout in ra-slam_amd/csrc/workspace.h;
 tests/cpp/test_workspace_score_layout.cc).  Not a GPU test: the header is plain C++ and the program needs nothing else.
 The measured size is where the carved parts end, the score table starts the buffer and the count lies behind it."""
 import subprocess
