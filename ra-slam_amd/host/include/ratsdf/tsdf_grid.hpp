@@ -2,6 +2,7 @@
 // forwarding to the C ABI of include/ratsdf.h.  The ABI library is bound at run time (dlopen), so
 // this host layer builds with g++ alone; the default binding is the in-tree HIP engine.
 #pragma once
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -13,77 +14,25 @@
 
 namespace ratsdf {
 
-// Entry points of include/ratsdf.h resolved from one shared library.
+// Every entry point this layer binds, X(name, required): ratsdf_<name> of the headers types.hpp includes.  A new one is
+// one row here.  Those of include/ratsdf.h are required; those of the feature headers (ratsdf_map.h, ratsdf_sample.h,
+// ...) are optional: the CPU oracle has none of them, and then the methods below report RATSDF_ERR_NOT_IMPLEMENTED.
+#define RATSDF_API_ENTRIES(X)                                                                                        \
+  X(create, 1) X(destroy, 1) X(integrate, 1) X(integrate_batch, 1) X(host_alloc, 1) X(host_free, 1)                  \
+  X(synchronize, 1) X(recover, 1) X(query, 1) X(gather_valid, 1) X(gather_valid_semantic, 1) X(download_all, 1)      \
+  X(raycast, 1) X(gather_valid_mesh, 1) X(download_all_mesh, 1) X(free_buffer, 1) X(num_active_blocks, 1)            \
+  X(status_string, 1) X(backend, 1)                                                                                  \
+  X(save_map, 0) X(load_map, 0) X(map_file_info, 0) X(sample_points, 0) X(esdf, 0) X(surface_points, 0)              \
+  X(surface_mesh, 0) X(cluster_mesh, 0) X(regions, 0) X(cost_to_go, 0)                                               \
+  X(labelset_create, 0) X(labelset_info_get, 0) X(labelset_destroy, 0) X(score_labels, 0)                            \
+  X(labelmesh_create, 0) X(labelmesh_info_get, 0) X(labelmesh_destroy, 0) X(score_mesh, 0)                           \
+  X(fuse_map, 0) X(fuse_blocks, 0) X(fuse_map_file, 0) X(fuse_map_transformed, 0) X(fuse_map_coarsened, 0)
+
+// The entry points resolved from one shared library; each member has the type of its prototype.
 struct Api {
-  int (*create)(float, float, int, ratsdf_engine**) = nullptr;
-  int (*destroy)(ratsdf_engine*) = nullptr;
-  int (*integrate)(ratsdf_engine*, const uint8_t*, const float*, const float*, const float*, int,
-                   int, float, const ratsdf_intrinsics*, const ratsdf_pose*) = nullptr;
-  int (*integrate_batch)(ratsdf_engine*, int, const uint8_t* const*, const float* const*,
-                         const float* const*, const float* const*, int, int, float,
-                         const ratsdf_intrinsics*, const ratsdf_pose*, int) = nullptr;
-  int (*host_alloc)(size_t, void**) = nullptr;
-  int (*host_free)(void*) = nullptr;
-  int (*synchronize)(ratsdf_engine*) = nullptr;
-  int (*recover)(ratsdf_engine*) = nullptr;
-  int (*query)(ratsdf_engine*, const ratsdf_bounds*, ratsdf_voxel_tsdf**, size_t*) = nullptr;
-  int (*gather_valid)(ratsdf_engine*, ratsdf_voxel_tsdf**, size_t*) = nullptr;
-  int (*gather_valid_semantic)(ratsdf_engine*, ratsdf_voxel_segm**, size_t*) = nullptr;
-  int (*download_all)(ratsdf_engine*, const char*) = nullptr;
-  int (*raycast)(ratsdf_engine*, const ratsdf_intrinsics*, int, int, const ratsdf_pose*, float,
-                 uint8_t*, uint8_t*) = nullptr;
-  int (*gather_valid_mesh)(ratsdf_engine*, float**, size_t*, int32_t**, size_t*, float**) = nullptr;
-  int (*download_all_mesh)(ratsdf_engine*, const char*, const char*, const char*) = nullptr;
-  int (*free_buffer)(void*) = nullptr;
-  int (*num_active_blocks)(ratsdf_engine*, int32_t*) = nullptr;
-  const char* (*status_string)(int) = nullptr;
-  const char* (*backend)() = nullptr;
-  // include/ratsdf_map.h: resolved when the library has them (the CPU oracle does not: then nullptr, and the
-  // calls below report RATSDF_ERR_NOT_IMPLEMENTED)
-  int (*save_map)(ratsdf_engine*, const char*) = nullptr;
-  int (*load_map)(ratsdf_engine*, const char*) = nullptr;
-  int (*map_file_info)(const char*, ratsdf_config*, int64_t*) = nullptr;
-  // include/ratsdf_sample.h: likewise optional (not in the CPU oracle)
-  int (*sample_points)(ratsdf_engine*, const float*, size_t, ratsdf_sample*) = nullptr;
-  // include/ratsdf_esdf.h: likewise optional (not in the CPU oracle)
-  int (*esdf)(ratsdf_engine*, const int32_t*, const int32_t*, float, uint32_t, float*, uint8_t*) = nullptr;
-  // include/ratsdf_surface.h: likewise optional (not in the CPU oracle)
-  int (*surface_points)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_surface_params*,
-                        ratsdf_surface_point**, size_t*) = nullptr;
-  // include/ratsdf_surface_mesh.h: likewise optional (not in the CPU oracle)
-  int (*surface_mesh)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_surface_mesh_params*,
-                      ratsdf_surface_point**, size_t*, int32_t**, size_t*) = nullptr;
-  // include/ratsdf_cluster_mesh.h: likewise optional (not in the CPU oracle)
-  int (*cluster_mesh)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_cluster_mesh_params*,
-                      ratsdf_surface_point**, size_t*, int32_t**, size_t*) = nullptr;
-  // include/ratsdf_regions.h: likewise optional (not in the CPU oracle)
-  int (*regions)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_regions_params*, int32_t*,
-                 ratsdf_region**, size_t*) = nullptr;
-  // include/ratsdf_cost.h: likewise optional (not in the CPU oracle)
-  int (*cost_to_go)(ratsdf_engine*, const int32_t*, const int32_t*, const ratsdf_cost_params*, const int32_t*, int32_t,
-                    uint32_t*, uint8_t*, ratsdf_cost_summary*) = nullptr;
-  // include/ratsdf_score.h: likewise optional (not in the CPU oracle)
-  int (*labelset_create)(ratsdf_engine*, const float*, const uint8_t*, size_t, float, ratsdf_labelset**) = nullptr;
-  int (*labelset_info_get)(const ratsdf_labelset*, ratsdf_labelset_info*) = nullptr;
-  int (*labelset_destroy)(ratsdf_labelset*) = nullptr;
-  int (*score_labels)(ratsdf_engine*, const ratsdf_labelset*, const ratsdf_score_params*, ratsdf_label_score*,
-                      ratsdf_voxel_label**, size_t*) = nullptr;
-  // include/ratsdf_score_mesh.h: likewise optional (not in the CPU oracle)
-  int (*labelmesh_create)(ratsdf_engine*, const float*, const uint8_t*, size_t, const int32_t*, size_t, float,
-                          ratsdf_labelmesh**) = nullptr;
-  int (*labelmesh_info_get)(const ratsdf_labelmesh*, ratsdf_labelmesh_info*) = nullptr;
-  int (*labelmesh_destroy)(ratsdf_labelmesh*) = nullptr;
-  int (*score_mesh)(ratsdf_engine*, const ratsdf_labelmesh*, const ratsdf_score_params*, ratsdf_label_score*,
-                    ratsdf_voxel_label**, size_t*) = nullptr;
-  // include/ratsdf_fuse.h: likewise optional (not in the CPU oracle)
-  int (*fuse_map)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
-  int (*fuse_blocks)(ratsdf_engine*, int32_t, const int16_t*, const float*, const ratsdf_rgbw*, const float*,
-                     ratsdf_fuse_stats*) = nullptr;
-  int (*fuse_map_file)(ratsdf_engine*, const char*, ratsdf_fuse_stats*) = nullptr;
-  // include/ratsdf_resample.h: likewise optional
-  int (*fuse_map_transformed)(ratsdf_engine*, ratsdf_engine*, const ratsdf_pose*, ratsdf_fuse_stats*) = nullptr;
-  // include/ratsdf_coarsen.h: likewise optional
-  int (*fuse_map_coarsened)(ratsdf_engine*, ratsdf_engine*, ratsdf_fuse_stats*) = nullptr;
+#define X(name, required) decltype(&ratsdf_##name) name = nullptr;
+  RATSDF_API_ENTRIES(X)
+#undef X
   void* handle = nullptr;
 
   // path == nullptr: $RATSDF_LIB or libratsdf.so next to this layer.  The symbol prefix is "ratsdf_"
@@ -92,63 +41,54 @@ struct Api {
   static const Api& Load(const char* path = nullptr, const char* prefix = RATSDF_ABI_PREFIX);
 };
 
-// Labelled points on the device (include/ratsdf_score.h): made by TSDFGrid::MakeLabelSet / TSDFSystem::MakeLabelSet,
-// immutable, destroyed with the object.  It belongs to the device, not to the grid that made it: any grid of that
-// device may score against it, and it may outlive them.
-class LabelSet {
+// Labelled records on the device, the common part of LabelSet and LabelMesh: the handle, its release and its info
+// through the two Api members given.
+template <class Handle, class Info, auto destroy, auto info_get>
+class LabelHandle {
  public:
-  LabelSet() = default;
-  ~LabelSet() { reset(); }
-  LabelSet(LabelSet&& o) noexcept : api_(o.api_), set_(o.set_) { o.set_ = nullptr; }
-  LabelSet& operator=(LabelSet&& o) noexcept {
+  LabelHandle() = default;
+  ~LabelHandle() { reset(); }
+  LabelHandle(LabelHandle&& o) noexcept : api_(o.api_), handle_(o.handle_) { o.handle_ = nullptr; }
+  LabelHandle& operator=(LabelHandle&& o) noexcept {
     if (this != &o) {
       reset();
-      api_ = o.api_, set_ = o.set_;
-      o.set_ = nullptr;
+      api_ = o.api_, handle_ = o.handle_;
+      o.handle_ = nullptr;
     }
     return *this;
   }
-  LabelSet(const LabelSet&) = delete;
-  LabelSet& operator=(const LabelSet&) = delete;
-  void reset();
-  bool valid() const { return set_ != nullptr; }
-  ratsdf_labelset* handle() const { return set_; }
-  ratsdf_labelset_info info() const;  // (zeros when there is no set)
+  LabelHandle(const LabelHandle&) = delete;
+  LabelHandle& operator=(const LabelHandle&) = delete;
+  void reset() {
+    if (handle_ && api_ && api_->*destroy) (api_->*destroy)(handle_);
+    handle_ = nullptr;
+  }
+  bool valid() const { return handle_ != nullptr; }
+  Handle* handle() const { return handle_; }
+  Info info() const {  // (zeros when there is none)
+    Info i;
+    memset(&i, 0, sizeof(i));
+    if (handle_ && api_ && api_->*info_get) (api_->*info_get)(handle_, &i);
+    return i;
+  }
 
  private:
   friend class TSDFGrid;
   const Api* api_ = nullptr;
-  ratsdf_labelset* set_ = nullptr;
+  Handle* handle_ = nullptr;
 };
+
+// Labelled points on the device (include/ratsdf_score.h): made by TSDFGrid::MakeLabelSet / TSDFSystem::MakeLabelSet,
+// immutable, destroyed with the object.  It belongs to the device, not to the grid that made it: any grid of that
+// device may score against it, and it may outlive them.
+class LabelSet
+    : public LabelHandle<ratsdf_labelset, ratsdf_labelset_info, &Api::labelset_destroy, &Api::labelset_info_get> {};
 
 // A labelled triangle mesh on the device (include/ratsdf_score_mesh.h): made by TSDFGrid::MakeLabelMesh /
 // TSDFSystem::MakeLabelMesh, immutable, destroyed with the object.  Like a LabelSet it belongs to the device, not to
 // the grid that made it.
-class LabelMesh {
- public:
-  LabelMesh() = default;
-  ~LabelMesh() { reset(); }
-  LabelMesh(LabelMesh&& o) noexcept : api_(o.api_), mesh_(o.mesh_) { o.mesh_ = nullptr; }
-  LabelMesh& operator=(LabelMesh&& o) noexcept {
-    if (this != &o) {
-      reset();
-      api_ = o.api_, mesh_ = o.mesh_;
-      o.mesh_ = nullptr;
-    }
-    return *this;
-  }
-  LabelMesh(const LabelMesh&) = delete;
-  LabelMesh& operator=(const LabelMesh&) = delete;
-  void reset();
-  bool valid() const { return mesh_ != nullptr; }
-  ratsdf_labelmesh* handle() const { return mesh_; }
-  ratsdf_labelmesh_info info() const;  // (zeros when there is no mesh)
-
- private:
-  friend class TSDFGrid;
-  const Api* api_ = nullptr;
-  ratsdf_labelmesh* mesh_ = nullptr;
-};
+class LabelMesh : public LabelHandle<ratsdf_labelmesh, ratsdf_labelmesh_info, &Api::labelmesh_destroy,
+                                     &Api::labelmesh_info_get> {};
 
 class TSDFGrid {
  public:
@@ -269,6 +209,32 @@ class TSDFGrid {
 
  private:
   void note(int st, const char* what);
+  // the guarded call of an optional entry point `f` on the engine: without an engine RATSDF_ERR_BAD_ARGUMENT, without
+  // the entry point RATSDF_ERR_NOT_IMPLEMENTED, else its status, noted under `what`.  Returns last_status().
+  template <class F, class... Args>
+  int call(const char* what, F f, Args... args) {
+    if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+    note(f ? f(engine_, args...) : RATSDF_ERR_NOT_IMPLEMENTED, what);
+    return status_;
+  }
+  // a result buffer of the library into *out (when the call succeeded and *out is wanted), freed on every path
+  template <class T>
+  void take(T* buf, size_t n, std::vector<T>* out) {
+    if (status_ == RATSDF_OK && out) out->assign(buf, buf + (buf ? n : 0));
+    if (buf) api_->free_buffer(buf);
+  }
+  // the bodies of the three Gather*, SurfaceMesh / ClusterMesh, ScoreLabels / ScoreMesh and MakeLabelSet /
+  // MakeLabelMesh (tsdf_host.cc)
+  template <class T, class F, class... Args>
+  std::vector<T> gather(const char* what, F f, Args... args);
+  template <class F, class Params>
+  int mesh(const char* what, F f, const int32_t origin[3], const int32_t dims[3], const Params& params,
+           std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles);
+  template <class F, class Labelled>
+  int score(const char* what, F f, const Labelled& labelled, const ratsdf_score_params& params,
+            ratsdf_label_score* out, std::vector<ratsdf_voxel_label>* per_voxel);
+  template <class Labelled, class F, class... Args>
+  int make_labelled(const char* what, Labelled* out, F f, Args... args);
   const Api* api_;
   ratsdf_engine* engine_ = nullptr;
   int status_ = 0;

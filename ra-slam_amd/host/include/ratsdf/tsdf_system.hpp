@@ -202,6 +202,17 @@ class TSDFSystem {
 
  private:
   void Run();
+  // f(tsdf_) under the engine's mutex: the map as integrated so far; flushed: after Flush(), every queued frame in it
+  template <class F>
+  auto read(F f) {
+    std::lock_guard<std::mutex> lock(mtx_read_);
+    return f(tsdf_);
+  }
+  template <class F>
+  auto flushed(F f) {
+    Flush();
+    return read(f);
+  }
   static constexpr size_t kMaxBatch = 32;  // frames per engine call (uploads run ahead inside the call)
   TSDFGrid tsdf_;
   HostBlockPool pool_;

@@ -42,61 +42,18 @@ const Api& Api::Load(const char* path, const char* prefix) {
     fprintf(stderr, "[ratsdf] cannot load %s: %s\n", lib.c_str(), dlerror());
     abort();  // no fallback: the HIP engine is the only implementation of the product path
   }
-  auto sym = [&](const char* name) {
+  auto sym = [&](const char* name, bool required) {
     const std::string full = std::string(prefix) + name;
     void* p = dlsym(api.handle, full.c_str());
-    if (!p) {
+    if (!p && required) {
       fprintf(stderr, "[ratsdf] %s does not export %s\n", lib.c_str(), full.c_str());
       abort();
     }
     return p;
   };
-  api.create = reinterpret_cast<decltype(api.create)>(sym("create"));
-  api.destroy = reinterpret_cast<decltype(api.destroy)>(sym("destroy"));
-  api.integrate = reinterpret_cast<decltype(api.integrate)>(sym("integrate"));
-  api.integrate_batch = reinterpret_cast<decltype(api.integrate_batch)>(sym("integrate_batch"));
-  api.host_alloc = reinterpret_cast<decltype(api.host_alloc)>(sym("host_alloc"));
-  api.host_free = reinterpret_cast<decltype(api.host_free)>(sym("host_free"));
-  api.synchronize = reinterpret_cast<decltype(api.synchronize)>(sym("synchronize"));
-  api.recover = reinterpret_cast<decltype(api.recover)>(sym("recover"));
-  api.query = reinterpret_cast<decltype(api.query)>(sym("query"));
-  api.gather_valid = reinterpret_cast<decltype(api.gather_valid)>(sym("gather_valid"));
-  api.gather_valid_semantic =
-      reinterpret_cast<decltype(api.gather_valid_semantic)>(sym("gather_valid_semantic"));
-  api.download_all = reinterpret_cast<decltype(api.download_all)>(sym("download_all"));
-  api.raycast = reinterpret_cast<decltype(api.raycast)>(sym("raycast"));
-  api.gather_valid_mesh =
-      reinterpret_cast<decltype(api.gather_valid_mesh)>(sym("gather_valid_mesh"));
-  api.download_all_mesh =
-      reinterpret_cast<decltype(api.download_all_mesh)>(sym("download_all_mesh"));
-  api.free_buffer = reinterpret_cast<decltype(api.free_buffer)>(sym("free_buffer"));
-  api.num_active_blocks = reinterpret_cast<decltype(api.num_active_blocks)>(sym("num_active_blocks"));
-  api.status_string = reinterpret_cast<decltype(api.status_string)>(sym("status_string"));
-  api.backend = reinterpret_cast<decltype(api.backend)>(sym("backend"));
-  auto opt_sym = [&](const char* name) { return dlsym(api.handle, (std::string(prefix) + name).c_str()); };
-  api.save_map = reinterpret_cast<decltype(api.save_map)>(opt_sym("save_map"));
-  api.load_map = reinterpret_cast<decltype(api.load_map)>(opt_sym("load_map"));
-  api.map_file_info = reinterpret_cast<decltype(api.map_file_info)>(opt_sym("map_file_info"));
-  api.sample_points = reinterpret_cast<decltype(api.sample_points)>(opt_sym("sample_points"));
-  api.fuse_map = reinterpret_cast<decltype(api.fuse_map)>(opt_sym("fuse_map"));
-  api.fuse_blocks = reinterpret_cast<decltype(api.fuse_blocks)>(opt_sym("fuse_blocks"));
-  api.fuse_map_file = reinterpret_cast<decltype(api.fuse_map_file)>(opt_sym("fuse_map_file"));
-  api.fuse_map_transformed = reinterpret_cast<decltype(api.fuse_map_transformed)>(opt_sym("fuse_map_transformed"));
-  api.fuse_map_coarsened = reinterpret_cast<decltype(api.fuse_map_coarsened)>(opt_sym("fuse_map_coarsened"));
-  api.esdf = reinterpret_cast<decltype(api.esdf)>(opt_sym("esdf"));
-  api.surface_points = reinterpret_cast<decltype(api.surface_points)>(opt_sym("surface_points"));
-  api.surface_mesh = reinterpret_cast<decltype(api.surface_mesh)>(opt_sym("surface_mesh"));
-  api.cluster_mesh = reinterpret_cast<decltype(api.cluster_mesh)>(opt_sym("cluster_mesh"));
-  api.regions = reinterpret_cast<decltype(api.regions)>(opt_sym("regions"));
-  api.cost_to_go = reinterpret_cast<decltype(api.cost_to_go)>(opt_sym("cost_to_go"));
-  api.labelset_create = reinterpret_cast<decltype(api.labelset_create)>(opt_sym("labelset_create"));
-  api.labelset_info_get = reinterpret_cast<decltype(api.labelset_info_get)>(opt_sym("labelset_info_get"));
-  api.labelset_destroy = reinterpret_cast<decltype(api.labelset_destroy)>(opt_sym("labelset_destroy"));
-  api.score_labels = reinterpret_cast<decltype(api.score_labels)>(opt_sym("score_labels"));
-  api.labelmesh_create = reinterpret_cast<decltype(api.labelmesh_create)>(opt_sym("labelmesh_create"));
-  api.labelmesh_info_get = reinterpret_cast<decltype(api.labelmesh_info_get)>(opt_sym("labelmesh_info_get"));
-  api.labelmesh_destroy = reinterpret_cast<decltype(api.labelmesh_destroy)>(opt_sym("labelmesh_destroy"));
-  api.score_mesh = reinterpret_cast<decltype(api.score_mesh)>(opt_sym("score_mesh"));
+#define X(name, required) api.name = reinterpret_cast<decltype(api.name)>(sym(#name, required));
+  RATSDF_API_ENTRIES(X)
+#undef X
   return loaded.emplace(key, api).first->second;
 }
 
@@ -161,38 +118,28 @@ void TSDFGrid::RayCast(float max_depth, const CameraParams& cam, const SE3<float
        "RayCast");
 }
 
-std::vector<VoxelSpatialTSDF> TSDFGrid::GatherValid() {
-  std::vector<VoxelSpatialTSDF> out;
-  if (!engine_) return out;
-  ratsdf_voxel_tsdf* buf = nullptr;
+template <class T, class F, class... Args>
+std::vector<T> TSDFGrid::gather(const char* what, F f, Args... args) {
+  std::vector<T> out;
+  T* buf = nullptr;
   size_t n = 0;
-  note(api_->gather_valid(engine_, &buf, &n), "GatherValid");
-  if (status_ == RATSDF_OK) out.assign(buf, buf + n);
-  if (buf) api_->free_buffer(buf);
+  if (!engine_) return out;
+  call(what, f, args..., &buf, &n);
+  take(buf, n, &out);
   return out;
+}
+
+std::vector<VoxelSpatialTSDF> TSDFGrid::GatherValid() {
+  return gather<VoxelSpatialTSDF>("GatherValid", api_->gather_valid);
 }
 
 std::vector<VoxelSpatialTSDFSEGM> TSDFGrid::GatherValidSemantic() {
-  std::vector<VoxelSpatialTSDFSEGM> out;
-  if (!engine_) return out;
-  ratsdf_voxel_segm* buf = nullptr;
-  size_t n = 0;
-  note(api_->gather_valid_semantic(engine_, &buf, &n), "GatherValidSemantic");
-  if (status_ == RATSDF_OK) out.assign(buf, buf + n);
-  if (buf) api_->free_buffer(buf);
-  return out;
+  return gather<VoxelSpatialTSDFSEGM>("GatherValidSemantic", api_->gather_valid_semantic);
 }
 
 std::vector<VoxelSpatialTSDF> TSDFGrid::GatherVoxels(const BoundingCube<float>& v) {
-  std::vector<VoxelSpatialTSDF> out;
-  if (!engine_) return out;
   const ratsdf_bounds b{v.xmin, v.xmax, v.ymin, v.ymax, v.zmin, v.zmax};
-  ratsdf_voxel_tsdf* buf = nullptr;
-  size_t n = 0;
-  note(api_->query(engine_, &b, &buf, &n), "GatherVoxels");
-  if (status_ == RATSDF_OK) out.assign(buf, buf + n);
-  if (buf) api_->free_buffer(buf);
-  return out;
+  return gather<VoxelSpatialTSDF>("GatherVoxels", api_->query, &b);
 }
 
 void TSDFGrid::GatherValidMesh(std::vector<float>* vb, std::vector<int32_t>* ib,
@@ -201,15 +148,10 @@ void TSDFGrid::GatherValidMesh(std::vector<float>* vb, std::vector<int32_t>* ib,
   float *v = nullptr, *p = nullptr;
   int32_t* idx = nullptr;
   size_t nv = 0, nt = 0;
-  note(api_->gather_valid_mesh(engine_, &v, &nv, &idx, &nt, &p), "GatherValidMesh");
-  if (status_ == RATSDF_OK) {
-    vb->assign(v, v + nv * 3);
-    pb->assign(p, p + nv);
-    ib->assign(idx, idx + nt * 3);
-  }
-  if (v) api_->free_buffer(v);
-  if (p) api_->free_buffer(p);
-  if (idx) api_->free_buffer(idx);
+  call("GatherValidMesh", api_->gather_valid_mesh, &v, &nv, &idx, &nt, &p);
+  take(v, nv * 3, vb);
+  take(p, nv, pb);
+  take(idx, nt * 3, ib);
 }
 
 void TSDFGrid::DownloadAllMesh(const std::string& vp, const std::string& ip, const std::string& pp) {
@@ -230,145 +172,100 @@ bool TSDFGrid::Recover() {
   return status_ == RATSDF_OK;
 }
 
-int TSDFGrid::SaveMap(const std::string& path) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->save_map ? api_->save_map(engine_, path.c_str()) : RATSDF_ERR_NOT_IMPLEMENTED, "SaveMap");
-  return status_;
-}
+int TSDFGrid::SaveMap(const std::string& path) { return call("SaveMap", api_->save_map, path.c_str()); }
 
-int TSDFGrid::LoadMap(const std::string& path) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->load_map ? api_->load_map(engine_, path.c_str()) : RATSDF_ERR_NOT_IMPLEMENTED, "LoadMap");
-  return status_;
-}
+int TSDFGrid::LoadMap(const std::string& path) { return call("LoadMap", api_->load_map, path.c_str()); }
 
 int TSDFGrid::SamplePoints(const float* xyz, size_t n, ratsdf_sample* out) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->sample_points ? api_->sample_points(engine_, xyz, n, out) : RATSDF_ERR_NOT_IMPLEMENTED, "SamplePoints");
-  return status_;
+  return call("SamplePoints", api_->sample_points, xyz, n, out);
 }
 
 int TSDFGrid::FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats) {
-  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->fuse_map ? api_->fuse_map(engine_, src.engine_, stats) : RATSDF_ERR_NOT_IMPLEMENTED, "FuseMap");
-  return status_;
+  if (!src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  return call("FuseMap", api_->fuse_map, src.engine_, stats);
 }
 
 int TSDFGrid::FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw,
                          const float* prob, ratsdf_fuse_stats* stats) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->fuse_blocks ? api_->fuse_blocks(engine_, n, block_pos, tsdf, rgbw, prob, stats) : RATSDF_ERR_NOT_IMPLEMENTED,
-       "FuseBlocks");
-  return status_;
+  return call("FuseBlocks", api_->fuse_blocks, n, block_pos, tsdf, rgbw, prob, stats);
 }
 
 int TSDFGrid::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->fuse_map_file ? api_->fuse_map_file(engine_, path.c_str(), stats) : RATSDF_ERR_NOT_IMPLEMENTED,
-       "FuseMapFile");
-  return status_;
+  return call("FuseMapFile", api_->fuse_map_file, path.c_str(), stats);
 }
 
 int TSDFGrid::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats) {
-  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->fuse_map_transformed ? api_->fuse_map_transformed(engine_, src.engine_, &dst_T_src, stats)
-                                  : RATSDF_ERR_NOT_IMPLEMENTED,
-       "FuseMapTransformed");
-  return status_;
+  if (!src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  return call("FuseMapTransformed", api_->fuse_map_transformed, src.engine_, &dst_T_src, stats);
 }
 
 int TSDFGrid::FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats) {
-  if (!engine_ || !src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->fuse_map_coarsened ? api_->fuse_map_coarsened(engine_, src.engine_, stats) : RATSDF_ERR_NOT_IMPLEMENTED,
-       "FuseMapCoarsened");
-  return status_;
+  if (!src.engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  return call("FuseMapCoarsened", api_->fuse_map_coarsened, src.engine_, stats);
 }
 
 int TSDFGrid::ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
                    uint8_t* state) {
-  if (!engine_) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  note(api_->esdf ? api_->esdf(engine_, origin, dims, occupied_below, flags, out, state) : RATSDF_ERR_NOT_IMPLEMENTED,
-       "ESDF");
-  return status_;
+  return call("ESDF", api_->esdf, origin, dims, occupied_below, flags, out, state);
 }
 
 int TSDFGrid::SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
                             std::vector<ratsdf_surface_point>* out) {
   if (out) out->clear();
-  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  if (!out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
   ratsdf_surface_point* buf = nullptr;
   size_t n = 0;
-  note(api_->surface_points ? api_->surface_points(engine_, origin, dims, &params, &buf, &n)
-                            : RATSDF_ERR_NOT_IMPLEMENTED,
-       "SurfacePoints");
-  if (status_ == RATSDF_OK && buf) {
-    out->assign(buf, buf + n);
-    api_->free_buffer(buf);
-  }
+  call("SurfacePoints", api_->surface_points, origin, dims, &params, &buf, &n);
+  take(buf, n, out);
+  return status_;
+}
+
+template <class F, class Params>
+int TSDFGrid::mesh(const char* what, F f, const int32_t origin[3], const int32_t dims[3], const Params& params,
+                   std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
+  if (vertices) vertices->clear();
+  if (triangles) triangles->clear();
+  if (!vertices || !triangles) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_surface_point* v = nullptr;
+  int32_t* t = nullptr;
+  size_t nv = 0, nt = 0;
+  call(what, f, origin, dims, &params, &v, &nv, &t, &nt);
+  take(v, nv, vertices);
+  take(t, 3 * nt, triangles);
   return status_;
 }
 
 int TSDFGrid::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
                           std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
-  if (vertices) vertices->clear();
-  if (triangles) triangles->clear();
-  if (!engine_ || !vertices || !triangles) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_surface_point* v = nullptr;
-  int32_t* t = nullptr;
-  size_t nv = 0, nt = 0;
-  note(api_->surface_mesh ? api_->surface_mesh(engine_, origin, dims, &params, &v, &nv, &t, &nt)
-                          : RATSDF_ERR_NOT_IMPLEMENTED,
-       "SurfaceMesh");
-  if (status_ == RATSDF_OK) {
-    if (v) vertices->assign(v, v + nv);
-    if (t) triangles->assign(t, t + 3 * nt);
-  }
-  if (v) api_->free_buffer(v);
-  if (t) api_->free_buffer(t);
-  return status_;
+  return mesh("SurfaceMesh", api_->surface_mesh, origin, dims, params, vertices, triangles);
 }
 
 int TSDFGrid::ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
                           std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
-  if (vertices) vertices->clear();
-  if (triangles) triangles->clear();
-  if (!engine_ || !vertices || !triangles) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_surface_point* v = nullptr;
-  int32_t* t = nullptr;
-  size_t nv = 0, nt = 0;
-  note(api_->cluster_mesh ? api_->cluster_mesh(engine_, origin, dims, &params, &v, &nv, &t, &nt)
-                          : RATSDF_ERR_NOT_IMPLEMENTED,
-       "ClusterMesh");
-  if (status_ == RATSDF_OK) {
-    if (v) vertices->assign(v, v + nv);
-    if (t) triangles->assign(t, t + 3 * nt);
-  }
-  if (v) api_->free_buffer(v);
-  if (t) api_->free_buffer(t);
-  return status_;
+  return mesh("ClusterMesh", api_->cluster_mesh, origin, dims, params, vertices, triangles);
 }
+
+namespace {
+// the voxels of a box for the caller's per-voxel buffers; a box beyond the headers' limits gets a one-voxel
+// placeholder: the library refuses it
+size_t box_voxels(const int32_t dims[3]) {
+  size_t n = 1;
+  for (int a = 0; dims && a < 3; ++a) n = dims[a] >= 1 && dims[a] <= 1024 && n ? n * (size_t)dims[a] : 0;
+  return dims && n && n <= ((size_t)1 << 27) ? n : 1;
+}
+}  // namespace
 
 int TSDFGrid::Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
                       std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
   if (labels) labels->clear();
   if (regions) regions->clear();
   if (!engine_ || !regions) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  if (labels) {  // (a box beyond the header's limits gets a one-voxel placeholder: the library refuses it)
-    size_t n = 1;
-    for (int a = 0; dims && a < 3; ++a) n = dims[a] >= 1 && dims[a] <= 1024 && n ? n * (size_t)dims[a] : 0;
-    labels->resize(dims && n && n <= ((size_t)1 << 27) ? n : 1);
-  }
+  if (labels) labels->resize(box_voxels(dims));
   ratsdf_region* r = nullptr;
   size_t nr = 0;
-  note(api_->regions ? api_->regions(engine_, origin, dims, &params, labels ? labels->data() : nullptr, &r, &nr)
-                     : RATSDF_ERR_NOT_IMPLEMENTED,
-       "Regions");
-  if (status_ == RATSDF_OK) {
-    if (r) regions->assign(r, r + nr);
-  } else if (labels) {
-    labels->clear();
-  }
-  if (r) api_->free_buffer(r);
+  call("Regions", api_->regions, origin, dims, &params, labels ? labels->data() : nullptr, &r, &nr);
+  take(r, nr, regions);
+  if (status_ != RATSDF_OK && labels) labels->clear();
   return status_;
 }
 
@@ -378,17 +275,12 @@ int TSDFGrid::CostToGo(const int32_t origin[3], const int32_t dims[3], const rat
   if (cost) cost->clear();
   if (next) next->clear();
   if (!engine_ || !cost) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  size_t n = 1;  // (a box beyond the header's limits gets a one-voxel placeholder: the library refuses it)
-  for (int a = 0; dims && a < 3; ++a) n = dims[a] >= 1 && dims[a] <= 1024 && n ? n * (size_t)dims[a] : 0;
-  n = dims && n && n <= ((size_t)1 << 27) ? n : 1;
-  cost->resize(n);
-  if (next) next->resize(n);
+  cost->resize(box_voxels(dims));
+  if (next) next->resize(cost->size());
   ratsdf_cost_summary s;
   memset(&s, 0, sizeof(s));
-  note(api_->cost_to_go ? api_->cost_to_go(engine_, origin, dims, &params, goals, n_goals, cost->data(),
-                                           next ? next->data() : nullptr, &s)
-                        : RATSDF_ERR_NOT_IMPLEMENTED,
-       "CostToGo");
+  call("CostToGo", api_->cost_to_go, origin, dims, &params, goals, n_goals, cost->data(),
+       next ? next->data() : nullptr, &s);
   if (status_ != RATSDF_OK) {
     cost->clear();
     if (next) next->clear();
@@ -398,81 +290,44 @@ int TSDFGrid::CostToGo(const int32_t origin[3], const int32_t dims[3], const rat
   return status_;
 }
 
-void LabelSet::reset() {
-  if (set_ && api_ && api_->labelset_destroy) api_->labelset_destroy(set_);
-  set_ = nullptr;
+template <class Labelled, class F, class... Args>
+int TSDFGrid::make_labelled(const char* what, Labelled* out, F f, Args... args) {
+  if (out) out->reset();
+  if (!out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  decltype(out->handle()) h = nullptr;
+  if (call(what, f, args..., &h) == RATSDF_OK) out->api_ = api_, out->handle_ = h;
+  return status_;
 }
 
-ratsdf_labelset_info LabelSet::info() const {
-  ratsdf_labelset_info i;
-  memset(&i, 0, sizeof(i));
-  if (set_ && api_ && api_->labelset_info_get) api_->labelset_info_get(set_, &i);
-  return i;
+template <class F, class Labelled>
+int TSDFGrid::score(const char* what, F f, const Labelled& labelled, const ratsdf_score_params& params,
+                    ratsdf_label_score* out, std::vector<ratsdf_voxel_label>* per_voxel) {
+  if (per_voxel) per_voxel->clear();
+  if (!out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  ratsdf_voxel_label* v = nullptr;
+  size_t nv = 0;
+  call(what, f, labelled.handle(), &params, out, per_voxel ? &v : nullptr, per_voxel ? &nv : nullptr);
+  take(v, nv, per_voxel);
+  return status_;
 }
 
 int TSDFGrid::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {
-  if (out) out->reset();
-  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_labelset* s = nullptr;
-  note(api_->labelset_create ? api_->labelset_create(engine_, xyz, labels, n, cell, &s) : RATSDF_ERR_NOT_IMPLEMENTED,
-       "MakeLabelSet");
-  if (status_ == RATSDF_OK) out->api_ = api_, out->set_ = s;
-  return status_;
+  return make_labelled("MakeLabelSet", out, api_->labelset_create, xyz, labels, n, cell);
 }
 
 int TSDFGrid::ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
                           std::vector<ratsdf_voxel_label>* per_voxel) {
-  if (per_voxel) per_voxel->clear();
-  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_voxel_label* v = nullptr;
-  size_t nv = 0;
-  note(api_->score_labels ? api_->score_labels(engine_, set.handle(), &params, out, per_voxel ? &v : nullptr,
-                                               per_voxel ? &nv : nullptr)
-                          : RATSDF_ERR_NOT_IMPLEMENTED,
-       "ScoreLabels");
-  if (status_ == RATSDF_OK && v) per_voxel->assign(v, v + nv);
-  if (v) api_->free_buffer(v);
-  return status_;
-}
-
-void LabelMesh::reset() {
-  if (mesh_ && api_ && api_->labelmesh_destroy) api_->labelmesh_destroy(mesh_);
-  mesh_ = nullptr;
-}
-
-ratsdf_labelmesh_info LabelMesh::info() const {
-  ratsdf_labelmesh_info i;
-  memset(&i, 0, sizeof(i));
-  if (mesh_ && api_ && api_->labelmesh_info_get) api_->labelmesh_info_get(mesh_, &i);
-  return i;
+  return score("ScoreLabels", api_->score_labels, set, params, out, per_voxel);
 }
 
 int TSDFGrid::MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri,
                             size_t n_triangles, float cell, LabelMesh* out) {
-  if (out) out->reset();
-  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_labelmesh* m = nullptr;
-  note(api_->labelmesh_create
-           ? api_->labelmesh_create(engine_, xyz, labels, n_vertices, tri, n_triangles, cell, &m)
-           : RATSDF_ERR_NOT_IMPLEMENTED,
-       "MakeLabelMesh");
-  if (status_ == RATSDF_OK) out->api_ = api_, out->mesh_ = m;
-  return status_;
+  return make_labelled("MakeLabelMesh", out, api_->labelmesh_create, xyz, labels, n_vertices, tri, n_triangles, cell);
 }
 
 int TSDFGrid::ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
                         std::vector<ratsdf_voxel_label>* per_voxel) {
-  if (per_voxel) per_voxel->clear();
-  if (!engine_ || !out) return status_ = RATSDF_ERR_BAD_ARGUMENT;
-  ratsdf_voxel_label* v = nullptr;
-  size_t nv = 0;
-  note(api_->score_mesh ? api_->score_mesh(engine_, mesh.handle(), &params, out, per_voxel ? &v : nullptr,
-                                           per_voxel ? &nv : nullptr)
-                        : RATSDF_ERR_NOT_IMPLEMENTED,
-       "ScoreMesh");
-  if (status_ == RATSDF_OK && v) per_voxel->assign(v, v + nv);
-  if (v) api_->free_buffer(v);
-  return status_;
+  return score("ScoreMesh", api_->score_mesh, mesh, params, out, per_voxel);
 }
 
 int TSDFGrid::NumActiveBlock() {
@@ -706,145 +561,113 @@ void TSDFSystem::Integrate(const SE3<float>& posecam_T_world, const Image& rgb, 
 }
 
 std::vector<VoxelSpatialTSDF> TSDFSystem::Query(const BoundingCube<float>& volumn) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.GatherVoxels(volumn);
+  return read([&](TSDFGrid& g) { return g.GatherVoxels(volumn); });
 }
 
 void TSDFSystem::Render(const CameraParams& virtual_cam, const SE3<float> cam_T_world,
                         uint8_t* img_rgba, uint8_t* img_normal) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  tsdf_.RayCast(max_depth_ * 2, virtual_cam, cam_T_world, img_rgba, img_normal);  // tsdf_module.cc:45-49
+  Render(virtual_cam, cam_T_world, img_rgba, img_normal, max_depth_ * 2);  // tsdf_module.cc:45-49
 }
 
 void TSDFSystem::Render(const CameraParams& virtual_cam, const SE3<float> cam_T_world,
                         uint8_t* img_rgba, uint8_t* img_normal, float max_depth) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  tsdf_.RayCast(max_depth, virtual_cam, cam_T_world, img_rgba, img_normal);       // tsdf_module.cc:51-55
+  read([&](TSDFGrid& g) { g.RayCast(max_depth, virtual_cam, cam_T_world, img_rgba, img_normal); });  // :51-55
 }
 
 int TSDFSystem::SaveMap(const std::string& path) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.SaveMap(path);
+  return flushed([&](TSDFGrid& g) { return g.SaveMap(path); });
 }
 
 int TSDFSystem::LoadMap(const std::string& path) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.LoadMap(path);
+  return flushed([&](TSDFGrid& g) { return g.LoadMap(path); });
 }
 
 int TSDFSystem::FuseMap(TSDFGrid& src, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.FuseMap(src, stats);
+  return flushed([&](TSDFGrid& g) { return g.FuseMap(src, stats); });
 }
 
 int TSDFSystem::FuseBlocks(int32_t n, const int16_t* block_pos, const float* tsdf, const ratsdf_rgbw* rgbw,
                            const float* prob, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.FuseBlocks(n, block_pos, tsdf, rgbw, prob, stats);
+  return flushed([&](TSDFGrid& g) { return g.FuseBlocks(n, block_pos, tsdf, rgbw, prob, stats); });
 }
 
 int TSDFSystem::FuseMapFile(const std::string& path, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.FuseMapFile(path, stats);
+  return flushed([&](TSDFGrid& g) { return g.FuseMapFile(path, stats); });
 }
 
 int TSDFSystem::FuseMapTransformed(TSDFGrid& src, const ratsdf_pose& dst_T_src, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.FuseMapTransformed(src, dst_T_src, stats);
+  return flushed([&](TSDFGrid& g) { return g.FuseMapTransformed(src, dst_T_src, stats); });
 }
 
 int TSDFSystem::FuseMapCoarsened(TSDFGrid& src, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.FuseMapCoarsened(src, stats);
+  return flushed([&](TSDFGrid& g) { return g.FuseMapCoarsened(src, stats); });
 }
 
 int TSDFSystem::CoarsenInto(TSDFGrid& dst, ratsdf_fuse_stats* stats) {
-  Flush();
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return dst.FuseMapCoarsened(tsdf_, stats);
+  return flushed([&](TSDFGrid& g) { return dst.FuseMapCoarsened(g, stats); });
 }
 
 int TSDFSystem::Sample(const float* xyz, size_t n, ratsdf_sample* out) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.SamplePoints(xyz, n, out);
+  return read([&](TSDFGrid& g) { return g.SamplePoints(xyz, n, out); });
 }
 
 int TSDFSystem::ESDF(const int32_t origin[3], const int32_t dims[3], float occupied_below, uint32_t flags, float* out,
                      uint8_t* state) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.ESDF(origin, dims, occupied_below, flags, out, state);
+  return read([&](TSDFGrid& g) { return g.ESDF(origin, dims, occupied_below, flags, out, state); });
 }
 
 int TSDFSystem::SurfacePoints(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_params& params,
                               std::vector<ratsdf_surface_point>* out) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.SurfacePoints(origin, dims, params, out);
+  return read([&](TSDFGrid& g) { return g.SurfacePoints(origin, dims, params, out); });
 }
 
 int TSDFSystem::SurfaceMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_surface_mesh_params& params,
                             std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.SurfaceMesh(origin, dims, params, vertices, triangles);
+  return read([&](TSDFGrid& g) { return g.SurfaceMesh(origin, dims, params, vertices, triangles); });
 }
 
 int TSDFSystem::ClusterMesh(const int32_t origin[3], const int32_t dims[3], const ratsdf_cluster_mesh_params& params,
                             std::vector<ratsdf_surface_point>* vertices, std::vector<int32_t>* triangles) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.ClusterMesh(origin, dims, params, vertices, triangles);
+  return read([&](TSDFGrid& g) { return g.ClusterMesh(origin, dims, params, vertices, triangles); });
 }
 
 int TSDFSystem::Regions(const int32_t origin[3], const int32_t dims[3], const ratsdf_regions_params& params,
                         std::vector<int32_t>* labels, std::vector<ratsdf_region>* regions) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.Regions(origin, dims, params, labels, regions);
+  return read([&](TSDFGrid& g) { return g.Regions(origin, dims, params, labels, regions); });
 }
 
 int TSDFSystem::CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params,
                          const int32_t* goals, int32_t n_goals, std::vector<uint32_t>* cost,
                          std::vector<uint8_t>* next, ratsdf_cost_summary* summary) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.CostToGo(origin, dims, params, goals, n_goals, cost, next, summary);
+  return read([&](TSDFGrid& g) { return g.CostToGo(origin, dims, params, goals, n_goals, cost, next, summary); });
 }
 
 int TSDFSystem::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.MakeLabelSet(xyz, labels, n, cell, out);
+  return read([&](TSDFGrid& g) { return g.MakeLabelSet(xyz, labels, n, cell, out); });
 }
 
 int TSDFSystem::ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,
                             std::vector<ratsdf_voxel_label>* per_voxel) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.ScoreLabels(set, params, out, per_voxel);
+  return read([&](TSDFGrid& g) { return g.ScoreLabels(set, params, out, per_voxel); });
 }
 
 int TSDFSystem::MakeLabelMesh(const float* xyz, const uint8_t* labels, size_t n_vertices, const int32_t* tri,
                               size_t n_triangles, float cell, LabelMesh* out) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.MakeLabelMesh(xyz, labels, n_vertices, tri, n_triangles, cell, out);
+  return read([&](TSDFGrid& g) { return g.MakeLabelMesh(xyz, labels, n_vertices, tri, n_triangles, cell, out); });
 }
 
 int TSDFSystem::ScoreMesh(const LabelMesh& mesh, const ratsdf_score_params& params, ratsdf_label_score* out,
                           std::vector<ratsdf_voxel_label>* per_voxel) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.ScoreMesh(mesh, params, out, per_voxel);
+  return read([&](TSDFGrid& g) { return g.ScoreMesh(mesh, params, out, per_voxel); });
 }
 
 void TSDFSystem::DownloadAll(const std::string& file_path) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  tsdf_.DownloadAll(file_path);
+  read([&](TSDFGrid& g) { g.DownloadAll(file_path); });
 }
 
 void TSDFSystem::DownloadAllMesh(const std::string& vertices_path, const std::string& indices_path,
                                  const std::string& prob_path) {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  tsdf_.DownloadAllMesh(vertices_path, indices_path, prob_path);
+  read([&](TSDFGrid& g) { g.DownloadAllMesh(vertices_path, indices_path, prob_path); });
 }
 
 void TSDFSystem::Run() {
@@ -954,8 +777,7 @@ size_t TSDFSystem::QueueSize() {
 }
 
 int TSDFSystem::NumActiveBlock() {
-  std::lock_guard<std::mutex> lock(mtx_read_);
-  return tsdf_.NumActiveBlock();
+  return read([](TSDFGrid& g) { return g.NumActiveBlock(); });
 }
 
 size_t TSDFSystem::frames_integrated() {

@@ -65,47 +65,22 @@ VOXEL_SEGM_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("tsdf", 
 assert BLOCK_DTYPE.itemsize == 12 and VOXEL_TSDF_DTYPE.itemsize == 16
 assert VOXEL_SEGM_DTYPE.itemsize == 20 and RGBW_DTYPE.itemsize == 4
 
-# every symbol include/ratsdf.h declares (without prefix)
-SYMBOLS = [
-    "create", "create_ex", "destroy", "integrate", "integrate_device", "integrate_device_batch",
-    "prepare_device_batch", "integrate_batch", "host_alloc", "host_free", "synchronize", "recover", "stream",
-    "profile_enable", "profile_read", "profile_read_frames", "totals", "pipeline_counters",
-    "num_active_blocks", "last_frame_stats", "query", "gather_valid", "gather_valid_semantic",
-    "download_all", "free_buffer", "raycast", "raycast_rows", "raycast_device", "gather_valid_mesh", "download_all_mesh",
-    "export_directory_device", "export_directory_delta_device", "import_blocks", "export_blocks_device",
-    "import_blocks_device", "group_create", "group_destroy", "group_size",
-    "group_integrate_device_batch", "group_synchronize", "group_profile_enable", "group_profile_read",
-    "test_allocate", "test_delete",
-    "test_retrieve", "test_assign_rgbw", "dump_directory", "dump_voxels", "dump_heap",
-    "status_string", "backend",
-]
-# include/ratsdf_map.h (map checkpoints): bound when the library has them -- the CPU oracle does not, and there the
-# methods raise RatsdfError with status 6 (not implemented)
-MAP_SYMBOLS = ["save_map", "load_map", "map_file_info"]
-# include/ratsdf_sample.h (batched point sampling): handled like MAP_SYMBOLS -- the oracle reports status 6
-SAMPLE_SYMBOLS = ["sample_points", "sample_points_device"]
-# ratsdf_sample (32 bytes); flags: SAMPLE_ALLOCATED | SAMPLE_OBSERVED | SAMPLE_NEAREST
+# The records, constants and parameter structs of the feature headers, header by header; their entry points are rows
+# of the ABI table below.
+# include/ratsdf_sample.h (batched point sampling): ratsdf_sample (32 bytes); flags: SAMPLE_ALLOCATED |
+# SAMPLE_OBSERVED | SAMPLE_NEAREST
 SAMPLE_DTYPE = np.dtype([("tsdf", "<f4"), ("grad", "<f4", (3,)), ("prob", "<f4"), ("rgbw", RGBW_DTYPE),
                          ("min_weight", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
 SAMPLE_ALLOCATED, SAMPLE_OBSERVED, SAMPLE_NEAREST = 1, 2, 4
 assert SAMPLE_DTYPE.itemsize == 32
-# include/ratsdf_esdf.h (Euclidean signed distance field over a box): handled like SAMPLE_SYMBOLS
-ESDF_SYMBOLS = ["esdf", "esdf_device"]
+# include/ratsdf_esdf.h (Euclidean signed distance field over a box)
 ESDF_UNKNOWN_OCCUPIED = 1
-# include/ratsdf_fuse.h (map fusion): handled like SAMPLE_SYMBOLS
-FUSE_SYMBOLS = ["fuse_map", "fuse_blocks", "fuse_blocks_device", "fuse_map_file"]
-# ratsdf_fuse_stats (40 bytes)
+ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
+# include/ratsdf_fuse.h (map fusion): ratsdf_fuse_stats (40 bytes)
 FUSE_STATS = np.dtype([("blocks_seen", "<i8"), ("blocks_allocated", "<i8"), ("blocks_skipped", "<i8"),
                        ("voxels_copied", "<i8"), ("voxels_averaged", "<i8")])
 assert FUSE_STATS.itemsize == 40
-# include/ratsdf_resample.h (transformed map fusion): handled like FUSE_SYMBOLS
-RESAMPLE_SYMBOLS = ["resample_blocks_device", "fuse_map_transformed"]
-# include/ratsdf_coarsen.h (map coarsening): handled like RESAMPLE_SYMBOLS
-COARSEN_SYMBOLS = ["coarsen_blocks_device", "fuse_map_coarsened"]
-ESDF_STATE_UNKNOWN, ESDF_STATE_FREE, ESDF_STATE_OCCUPIED = 0, 1, 2
-# include/ratsdf_surface.h (oriented surface points of a box): handled like ESDF_SYMBOLS
-SURFACE_SYMBOLS = ["surface_points", "surface_points_device"]
-# ratsdf_surface_point (32 bytes)
+# include/ratsdf_surface.h (oriented surface points of a box): ratsdf_surface_point (32 bytes)
 SURFACE_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("prob", "<f4"), ("rgbw", RGBW_DTYPE)])
 assert SURFACE_DTYPE.itemsize == 32
 
@@ -115,28 +90,18 @@ class SurfaceParams(C.Structure):
     _fields_ = [("min_weight", C.c_int32), ("min_prob", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-# include/ratsdf_surface_mesh.h (welded triangle mesh of a box): handled like SURFACE_SYMBOLS
-SURFACE_MESH_SYMBOLS = ["surface_mesh", "surface_mesh_device"]
-
-
 class SurfaceMeshParams(C.Structure):
-    """ratsdf_surface_mesh_params"""
+    """ratsdf_surface_mesh_params (include/ratsdf_surface_mesh.h: welded triangle mesh of a box)"""
     _fields_ = [("min_weight", C.c_int32), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
                 ("reserved1", C.c_uint32)]
 
 
-# include/ratsdf_cluster_mesh.h (clustered mesh of a box): handled like SURFACE_MESH_SYMBOLS
-CLUSTER_MESH_SYMBOLS = ["cluster_mesh", "cluster_mesh_device"]
-
-
 class ClusterMeshParams(C.Structure):
-    """ratsdf_cluster_mesh_params"""
+    """ratsdf_cluster_mesh_params (include/ratsdf_cluster_mesh.h: clustered mesh of a box)"""
     _fields_ = [("min_weight", C.c_int32), ("factor", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-# include/ratsdf_regions.h (connected regions of a box): handled like ESDF_SYMBOLS
-REGIONS_SYMBOLS = ["regions", "regions_device"]
-# ratsdf_region (32 bytes)
+# include/ratsdf_regions.h (connected regions of a box): ratsdf_region (32 bytes)
 REGION_DTYPE = np.dtype([("root", "<i4"), ("voxels", "<i4"), ("frontier", "<i4"), ("faces", "<u4"),
                          ("lo", "<i2", (3,)), ("hi", "<i2", (3,)), ("reserved", "<u4")])
 assert REGION_DTYPE.itemsize == 32
@@ -147,8 +112,7 @@ class RegionsParams(C.Structure):
     _fields_ = [("occupied_below", C.c_float), ("min_prob", C.c_float), ("states", C.c_uint32), ("flags", C.c_uint32)]
 
 
-# include/ratsdf_cost.h (cost-to-go field of a box): handled like ESDF_SYMBOLS
-COST_SYMBOLS = ["cost_to_go", "cost_to_go_device"]
+# include/ratsdf_cost.h (cost-to-go field of a box)
 COST_UNKNOWN_OCCUPIED, COST_THROUGH_UNKNOWN, COST_FACES_ONLY, COST_CONTINUE = 1, 2, 4, 8
 COST_NONE = 0xFFFFFFFF
 COST_AT_GOAL, COST_NO_STEP = 255, 254       # `next` bytes that are no direction code
@@ -169,9 +133,7 @@ class CostParams(C.Structure):
     _fields_ = [("occupied_below", C.c_float), ("clearance", C.c_float), ("flags", C.c_uint32), ("rounds", C.c_int32)]
 
 
-# include/ratsdf_score.h (label sets and the map's score against them): handled like ESDF_SYMBOLS
-SCORE_SYMBOLS = ["labelset_create", "labelset_create_device", "labelset_info_get", "labelset_destroy", "score_labels",
-                 "score_labels_device"]
+# include/ratsdf_score.h (label sets and the map's score against them)
 LABEL_IGNORE, LABEL_LOW, LABEL_HIGH = 0, 1, 2
 # ratsdf_label_score (4160 bytes) and ratsdf_voxel_label (8 bytes)
 LABEL_SCORE_DTYPE = np.dtype([("voxels", "<i8"), ("selected", "<i8"), ("unmatched", "<i8"), ("unannotated", "<i8"),
@@ -288,9 +250,7 @@ class LabelScore:
                 f"unannotated={self.unannotated}, confusion={self.confusion}, iou={self.iou:.6f})")
 
 
-# include/ratsdf_score_mesh.h (labelled triangle meshes and the map's score against them): handled like SCORE_SYMBOLS
-SCORE_MESH_SYMBOLS = ["labelmesh_create", "labelmesh_create_device", "labelmesh_info_get", "labelmesh_destroy",
-                      "score_mesh", "score_mesh_device"]
+# include/ratsdf_score_mesh.h (labelled triangle meshes and the map's score against them)
 LABELMESH_MAX_REFS = 1 << 25
 
 
@@ -353,6 +313,150 @@ def descend(next, origin, start, max_steps=None):
     return (np.asarray(path, dtype=np.int64) + np.asarray(origin, dtype=np.int64)).astype(np.int32).reshape(-1, 3)
 
 
+_vp, _str, _int, _i32, _i64, _u32, _f32, _size = (C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_uint32,
+                                                  C.c_float, C.c_size_t)
+_P = C.POINTER
+_frame = [_vp, _vp, _vp, _vp, _vp, _int, _int, _f32, _P(Intrinsics), _P(Pose)]          # one frame's images and camera
+_frames = [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _f32, _vp, _vp]                   # n frames: tables of them
+_view = [_vp, _P(Intrinsics), _int, _int, _P(Pose), _f32]                               # a ray cast's camera
+_box = [_vp, _P(_i32), _P(_i32)]                                                        # engine, origin[3], dims[3]
+_owned = [_P(_vp), _P(_size)]                      # a result buffer handed over: (pointer, count) out-parameters
+_profile = [_vp, _P(C.c_double), _P(_i64)]
+_mesh = _owned + _owned                                                                 # vertices, then triangles
+_mesh_device = [_vp, _i64, _vp, _i64, _vp]
+_labelset = [_vp, _vp, _vp, _size, _f32, _P(_vp)]
+_labelmesh = [_vp, _vp, _vp, _size, _vp, _size, _f32, _P(_vp)]
+_score = [_vp, _vp, _P(ScoreParams), _vp]
+
+# The shape of the C ABI: header -> {symbol (without prefix): argtypes}, in the headers' order.  A new entry point is
+# one row here.  ratsdf.h's symbols must all be exported; those of the other headers are bound when the library has
+# them -- the CPU oracle does not, and there they report status 6 (not implemented).
+ABI = {
+    "ratsdf.h": {
+        "create": [_f32, _f32, _int, _P(_vp)],
+        "create_ex": [_P(Config), _P(_vp)],
+        "destroy": [_vp],
+        "integrate": _frame,
+        "integrate_device": _frame,
+        "integrate_device_batch": _frames,
+        "prepare_device_batch": [_vp, _int, _int, _int],
+        "integrate_batch": _frames + [_int],
+        "host_alloc": [_size, _P(_vp)],
+        "host_free": [_vp],
+        "synchronize": [_vp],
+        "recover": [_vp],
+        "stream": [_vp, _P(_vp)],
+        "profile_enable": [_vp, _int],
+        "profile_read": _profile,
+        "profile_read_frames": [_vp, _P(_f32), _P(_f32), _int, _P(_int)],
+        "totals": [_vp, _P(_i64), _int],
+        "pipeline_counters": [_vp, _P(_i64), _int],
+        "num_active_blocks": [_vp, _P(_i32)],
+        "last_frame_stats": [_vp, _P(FrameStats)],
+        "query": [_vp, _P(Bounds)] + _owned,
+        "gather_valid": [_vp] + _owned,
+        "gather_valid_semantic": [_vp] + _owned,
+        "download_all": [_vp, _str],
+        "free_buffer": [_vp],
+        "raycast": _view + [_vp, _vp],
+        "raycast_rows": _view + [_int, _int, _vp, _vp],
+        "raycast_device": _view + [_vp, _vp],
+        "gather_valid_mesh": [_vp] + _mesh + [_P(_vp)],
+        "download_all_mesh": [_vp, _str, _str, _str],
+        "export_directory_device": [_vp, _vp, _i32, _vp],
+        "export_directory_delta_device": [_vp, _vp, _i32, _vp],
+        "import_blocks": [_vp, _i32, _vp, _vp, _vp, _vp],
+        "export_blocks_device": [_vp, _i32, _vp, _vp, _vp],
+        "import_blocks_device": [_vp, _i32, _vp, _vp],
+        "group_create": [_vp, _int, _P(_vp)],
+        "group_destroy": [_vp],
+        "group_size": [_vp, _P(_i32)],
+        "group_integrate_device_batch": _frames,
+        "group_synchronize": [_vp],
+        "group_profile_enable": [_vp, _int],
+        "group_profile_read": _profile,
+        "test_allocate": [_vp, _vp, _i32],
+        "test_delete": [_vp, _vp, _i32],
+        "test_retrieve": [_vp, _vp, _i32, _vp, _vp, _vp, _vp],
+        "test_assign_rgbw": [_vp, _vp, _vp, _i32],
+        "dump_directory": [_vp, _P(_vp), _P(_vp), _P(_size)],
+        "dump_voxels": [_vp, _vp, _i32, _vp, _vp, _vp],
+        "dump_heap": [_vp, _P(_i32), _vp],
+        "status_string": [_int],
+        "backend": [],
+    },
+    "ratsdf_map.h": {
+        "save_map": [_vp, _str],
+        "load_map": [_vp, _str],
+        "map_file_info": [_str, _P(Config), _P(_i64)],
+    },
+    "ratsdf_sample.h": {
+        "sample_points": [_vp, _vp, _size, _vp],
+        "sample_points_device": [_vp, _vp, _size, _vp],
+    },
+    "ratsdf_esdf.h": {
+        "esdf": _box + [_f32, _u32, _vp, _vp],
+        "esdf_device": _box + [_f32, _u32, _vp, _vp],
+    },
+    "ratsdf_fuse.h": {
+        "fuse_map": [_vp, _vp, _vp],
+        "fuse_blocks": [_vp, _i32, _vp, _vp, _vp, _vp, _vp],
+        "fuse_blocks_device": [_vp, _i32, _vp, _vp, _vp],
+        "fuse_map_file": [_vp, _str, _vp],
+    },
+    "ratsdf_resample.h": {
+        "resample_blocks_device": [_vp, _P(Pose), _i32, _vp, _vp, _vp],
+        "fuse_map_transformed": [_vp, _vp, _P(Pose), _vp],
+    },
+    "ratsdf_coarsen.h": {
+        "coarsen_blocks_device": [_vp, _i32, _vp, _vp, _vp],
+        "fuse_map_coarsened": [_vp, _vp, _vp],
+    },
+    "ratsdf_surface.h": {
+        "surface_points": _box + [_P(SurfaceParams)] + _owned,
+        "surface_points_device": _box + [_P(SurfaceParams), _vp, _i64, _vp],
+    },
+    "ratsdf_surface_mesh.h": {
+        "surface_mesh": _box + [_P(SurfaceMeshParams)] + _mesh,
+        "surface_mesh_device": _box + [_P(SurfaceMeshParams)] + _mesh_device,
+    },
+    "ratsdf_cluster_mesh.h": {
+        "cluster_mesh": _box + [_P(ClusterMeshParams)] + _mesh,
+        "cluster_mesh_device": _box + [_P(ClusterMeshParams)] + _mesh_device,
+    },
+    "ratsdf_regions.h": {
+        "regions": _box + [_P(RegionsParams), _vp] + _owned,
+        "regions_device": _box + [_P(RegionsParams), _vp, _vp, _i64, _vp],
+    },
+    "ratsdf_cost.h": {
+        "cost_to_go": _box + [_P(CostParams), _vp, _i32, _vp, _vp, _vp],
+        "cost_to_go_device": _box + [_P(CostParams), _vp, _i32, _vp, _vp, _vp],
+    },
+    "ratsdf_score.h": {
+        "labelset_create": _labelset,
+        "labelset_create_device": _labelset,
+        "labelset_info_get": [_vp, _P(LabelSetInfo)],
+        "labelset_destroy": [_vp],
+        "score_labels": _score + _owned,
+        "score_labels_device": _score + [_vp, _i64, _vp],
+    },
+    "ratsdf_score_mesh.h": {
+        "labelmesh_create": _labelmesh,
+        "labelmesh_create_device": _labelmesh,
+        "labelmesh_info_get": [_vp, _P(LabelMeshInfo)],
+        "labelmesh_destroy": [_vp],
+        "score_mesh": _score + _owned,
+        "score_mesh_device": _score + [_vp, _i64, _vp],
+    },
+}
+RESTYPE = {"status_string": _str, "backend": _str}      # every other entry point returns a status (int)
+
+# the symbols header by header: the table's keys
+(SYMBOLS, MAP_SYMBOLS, SAMPLE_SYMBOLS, ESDF_SYMBOLS, FUSE_SYMBOLS, RESAMPLE_SYMBOLS, COARSEN_SYMBOLS, SURFACE_SYMBOLS,
+ SURFACE_MESH_SYMBOLS, CLUSTER_MESH_SYMBOLS, REGIONS_SYMBOLS, COST_SYMBOLS, SCORE_SYMBOLS,
+ SCORE_MESH_SYMBOLS) = (list(table) for table in ABI.values())
+
+
 class Library:
     """A loaded shared library exporting the ABI under ``prefix``."""
 
@@ -361,212 +465,22 @@ class Library:
         self.prefix = prefix
         self.dll = C.CDLL(self.path)
         self.fn = {}
-        import os
-        for s in SYMBOLS:
-            try:
-                self.fn[s] = getattr(self.dll, prefix + s)  # AttributeError = missing export
-            except AttributeError:
-                # (same-box A/B against engine builds of earlier commits, tools/build_variant.sh: entry points
-                # added since are simply absent there; never set for the product library)
-                if os.environ.get("RATSDF_LIB_VARIANT") != "1":
-                    raise
-                self.fn[s] = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-        for s in SYMBOLS:
-            self.fn[s].restype = C.c_int
-        self.fn["status_string"].restype = C.c_char_p
-        self.fn["backend"].restype = C.c_char_p
-        vp = C.c_void_p
-        self.fn["create"].argtypes = [C.c_float, C.c_float, C.c_int, C.POINTER(vp)]
-        self.fn["create_ex"].argtypes = [C.POINTER(Config), C.POINTER(vp)]
-        self.fn["destroy"].argtypes = [vp]
-        self.fn["integrate"].argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float,
-                                         C.POINTER(Intrinsics), C.POINTER(Pose)]
-        self.fn["integrate_device"].argtypes = self.fn["integrate"].argtypes
-        self.fn["integrate_device_batch"].argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
-                                                      C.c_float, vp, vp]
-        self.fn["prepare_device_batch"].argtypes = [vp, C.c_int, C.c_int, C.c_int]
-        self.fn["integrate_batch"].argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float,
-                                               vp, vp, C.c_int]
-        self.fn["host_alloc"].argtypes = [C.c_size_t, C.POINTER(vp)]
-        self.fn["host_free"].argtypes = [vp]
-        self.fn["synchronize"].argtypes = [vp]
-        self.fn["recover"].argtypes = [vp]
-        self.fn["stream"].argtypes = [vp, C.POINTER(vp)]
-        self.fn["profile_enable"].argtypes = [vp, C.c_int]
-        self.fn["profile_read"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        self.fn["profile_read_frames"].argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
-                                                    C.POINTER(C.c_int)]
-        self.fn["totals"].argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
-        self.fn["pipeline_counters"].argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
-        self.fn["num_active_blocks"].argtypes = [vp, C.POINTER(C.c_int32)]
-        self.fn["last_frame_stats"].argtypes = [vp, C.POINTER(FrameStats)]
-        self.fn["query"].argtypes = [vp, C.POINTER(Bounds), C.POINTER(vp), C.POINTER(C.c_size_t)]
-        self.fn["gather_valid"].argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-        self.fn["gather_valid_semantic"].argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-        self.fn["download_all"].argtypes = [vp, C.c_char_p]
-        self.fn["free_buffer"].argtypes = [vp]
-        self.fn["raycast"].argtypes = [vp, C.POINTER(Intrinsics), C.c_int, C.c_int, C.POINTER(Pose),
-                                       C.c_float, vp, vp]
-        self.fn["raycast_device"].argtypes = self.fn["raycast"].argtypes
-        self.fn["raycast_rows"].argtypes = [vp, C.POINTER(Intrinsics), C.c_int, C.c_int, C.POINTER(Pose),
-                                            C.c_float, C.c_int, C.c_int, vp, vp]
-        self.fn["gather_valid_mesh"].argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t),
-                                                 C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
-        self.fn["download_all_mesh"].argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p]
-        self.fn["export_directory_device"].argtypes = [vp, vp, C.c_int32, vp]
-        self.fn["export_directory_delta_device"].argtypes = [vp, vp, C.c_int32, vp]
-        self.fn["import_blocks"].argtypes = [vp, C.c_int32, vp, vp, vp, vp]
-        self.fn["export_blocks_device"].argtypes = [vp, C.c_int32, vp, vp, vp]
-        self.fn["import_blocks_device"].argtypes = [vp, C.c_int32, vp, vp]
-        self.fn["group_create"].argtypes = [vp, C.c_int, C.POINTER(vp)]
-        self.fn["group_destroy"].argtypes = [vp]
-        self.fn["group_size"].argtypes = [vp, C.POINTER(C.c_int32)]
-        self.fn["group_integrate_device_batch"].argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int,
-                                                            C.c_int, C.c_float, vp, vp]
-        self.fn["group_synchronize"].argtypes = [vp]
-        self.fn["group_profile_enable"].argtypes = [vp, C.c_int]
-        self.fn["group_profile_read"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        self.fn["test_allocate"].argtypes = [vp, vp, C.c_int32]
-        self.fn["test_delete"].argtypes = [vp, vp, C.c_int32]
-        self.fn["test_retrieve"].argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
-        self.fn["test_assign_rgbw"].argtypes = [vp, vp, vp, C.c_int32]
-        self.fn["dump_directory"].argtypes = [vp, C.POINTER(vp), C.POINTER(vp),
-                                              C.POINTER(C.c_size_t)]
-        self.fn["dump_voxels"].argtypes = [vp, vp, C.c_int32, vp, vp, vp]
-        self.fn["dump_heap"].argtypes = [vp, C.POINTER(C.c_int32), vp]
-        self.fn["status_string"].argtypes = [C.c_int]
-        self.fn["backend"].argtypes = []
-        for s in MAP_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = {"save_map": [vp, C.c_char_p], "load_map": [vp, C.c_char_p],
-                              "map_file_info": [C.c_char_p, C.POINTER(Config), C.POINTER(C.c_int64)]}[s]
-            self.fn[s] = f
-        for s in SAMPLE_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = [vp, vp, C.c_size_t, vp]
-            self.fn[s] = f
-        for s in ESDF_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_uint32, vp, vp]
-            self.fn[s] = f
-        for s in SURFACE_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(SurfaceParams)]
-                f.argtypes = box + {"surface_points": [C.POINTER(vp), C.POINTER(C.c_size_t)],
-                                    "surface_points_device": [vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-        for s in SURFACE_MESH_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(SurfaceMeshParams)]
-                f.argtypes = box + {"surface_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
-                                                     C.POINTER(C.c_size_t)],
-                                    "surface_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-        for s in CLUSTER_MESH_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(ClusterMeshParams)]
-                f.argtypes = box + {"cluster_mesh": [C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
-                                                     C.POINTER(C.c_size_t)],
-                                    "cluster_mesh_device": [vp, C.c_int64, vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-        for s in REGIONS_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                box = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(RegionsParams)]
-                f.argtypes = box + {"regions": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
-                                    "regions_device": [vp, vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-        for s in COST_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(CostParams), vp, C.c_int32,
-                              vp, vp, vp]
-            self.fn[s] = f
-        for s in SCORE_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                sp = C.POINTER(ScoreParams)
-                f.argtypes = {"labelset_create": [vp, vp, vp, C.c_size_t, C.c_float, C.POINTER(vp)],
-                              "labelset_create_device": [vp, vp, vp, C.c_size_t, C.c_float, C.POINTER(vp)],
-                              "labelset_info_get": [vp, C.POINTER(LabelSetInfo)], "labelset_destroy": [vp],
-                              "score_labels": [vp, vp, sp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
-                              "score_labels_device": [vp, vp, sp, vp, vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-        for s in SCORE_MESH_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                sp = C.POINTER(ScoreParams)
-                make = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_float, C.POINTER(vp)]
-                f.argtypes = {"labelmesh_create": make, "labelmesh_create_device": make,
-                              "labelmesh_info_get": [vp, C.POINTER(LabelMeshInfo)], "labelmesh_destroy": [vp],
-                              "score_mesh": [vp, vp, sp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
-                              "score_mesh_device": [vp, vp, sp, vp, vp, C.c_int64, vp]}[s]
-            self.fn[s] = f
-
-        for s in FUSE_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = {"fuse_map": [vp, vp, vp], "fuse_blocks": [vp, C.c_int32, vp, vp, vp, vp, vp],
-                              "fuse_blocks_device": [vp, C.c_int32, vp, vp, vp],
-                              "fuse_map_file": [vp, C.c_char_p, vp]}[s]
-            self.fn[s] = f
-        for s in RESAMPLE_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = {"resample_blocks_device": [vp, C.POINTER(Pose), C.c_int32, vp, vp, vp],
-                              "fuse_map_transformed": [vp, vp, C.POINTER(Pose), vp]}[s]
-            self.fn[s] = f
-        for s in COARSEN_SYMBOLS:
-            f = getattr(self.dll, prefix + s, None)
-            if f is None:
-                f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
-            else:
-                f.restype = C.c_int
-                f.argtypes = {"coarsen_blocks_device": [vp, C.c_int32, vp, vp, vp],
-                              "fuse_map_coarsened": [vp, vp, vp]}[s]
-            self.fn[s] = f
+        for header, table in ABI.items():
+            core = header == "ratsdf.h"
+            for s, argtypes in table.items():
+                try:
+                    f = getattr(self.dll, prefix + s)  # AttributeError = missing export
+                except AttributeError:
+                    # (same-box A/B against engine builds of earlier commits, tools/build_variant.sh: entry points
+                    # of ratsdf.h added since are simply absent there; never set for the product library)
+                    if core and os.environ.get("RATSDF_LIB_VARIANT") != "1":
+                        raise
+                    f = C.CFUNCTYPE(C.c_int)(lambda *a: 6)
+                    if not core:
+                        argtypes = None
+                if argtypes is not None:
+                    f.restype, f.argtypes = RESTYPE.get(s, C.c_int), argtypes
+                self.fn[s] = f
 
     def backend(self):
         return self.fn["backend"]().decode()
@@ -593,6 +507,18 @@ def _box3(v, what):
     if np.any(a < -(1 << 31)) or np.any(a >= (1 << 31)):
         raise ValueError(f"{what} out of the int32 range")
     return (C.c_int32 * 3)(*(int(x) for x in a))
+
+
+def _box_shape(d):
+    """the (Z, Y, X) shape of the per-voxel output of a box with the three int32 dims `d`.  A box beyond the limits
+    gets a one-voxel placeholder: the library refuses it, status 1"""
+    n = int(np.prod([int(v) for v in d], dtype=object))
+    return tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+
+
+def _device_ptrs(*buffers):
+    """the raw pointer of every device buffer (torch tensor, devmem.DeviceArray or the pointer itself); None for 0"""
+    return [(v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0)) or None for v in buffers]
 
 
 def _esdf_flags(unknown_occupied):
@@ -854,23 +780,34 @@ class Engine:
             return np.empty(0, dtype=dtype)
         return np.asarray(_OwnedBuffer(self.lib, ptr.value, n * dtype.itemsize)).view(dtype)
 
+    def _call_owned(self, symbol, dtype, *args, wanted=True):
+        """calls an entry point whose last two arguments are the (pointer, count) out-parameters of a result buffer
+        (NULL for both unless `wanted`); returns the buffer as an array that owns it, or None"""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(self.lib.fn[symbol](self._h, *args, C.byref(p) if wanted else None, C.byref(n) if wanted else None),
+               symbol)
+        return self._take(p, n.value, dtype) if wanted else None
+
+    def _read_back(self, d_buffer, dtype, n=1):
+        """waits for the stream, then the first n `dtype` items of a device buffer that can be read from here: a torch
+        tensor or a devmem.DeviceArray.  None for a raw pointer: the caller reads it"""
+        self.synchronize()
+        if hasattr(d_buffer, "cpu"):         # a torch tensor
+            d_buffer = d_buffer.cpu()
+        if not hasattr(d_buffer, "numpy"):
+            return None
+        return d_buffer.numpy().reshape(-1).view(np.uint8)[:n * np.dtype(dtype).itemsize].view(dtype)
+
     def query(self, bounds):
         """TSDFSystem::Query / TSDFGrid::GatherVoxels (voxel_tsdf.cu:532-559)."""
         b = bounds if isinstance(bounds, Bounds) else Bounds(*[float(v) for v in bounds])
-        p, n = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["query"](self._h, C.byref(b), C.byref(p), C.byref(n)), "query")
-        return self._take(p, n.value, VOXEL_TSDF_DTYPE)
+        return self._call_owned("query", VOXEL_TSDF_DTYPE, C.byref(b))
 
     def gather_valid(self):
-        p, n = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["gather_valid"](self._h, C.byref(p), C.byref(n)), "gather_valid")
-        return self._take(p, n.value, VOXEL_TSDF_DTYPE)
+        return self._call_owned("gather_valid", VOXEL_TSDF_DTYPE)
 
     def gather_valid_semantic(self):
-        p, n = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["gather_valid_semantic"](self._h, C.byref(p), C.byref(n)),
-               "gather_valid_semantic")
-        return self._take(p, n.value, VOXEL_SEGM_DTYPE)
+        return self._call_owned("gather_valid_semantic", VOXEL_SEGM_DTYPE)
 
     def download_all(self, path):
         _check(self.lib.fn["download_all"](self._h, str(path).encode()), "download_all")
@@ -926,9 +863,7 @@ class Engine:
         (dims[2], dims[1], dims[0]) -- metres to the nearest obstacle voxel, negative inside obstacles -- and, with
         with_state, the uint8 ESDF_STATE_* of every voxel as a second array of the same shape."""
         o, d = _box3(origin, "origin"), _box3(dims, "dims")
-        n = int(np.prod([int(v) for v in d], dtype=object))
-        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
-        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+        shape = _box_shape(d)
         out = np.empty(shape, dtype=np.float32)
         state = np.empty(shape, dtype=np.uint8) if with_state else None
         _check(self.lib.fn["esdf"](self._h, o, d, C.c_float(occupied_below), _esdf_flags(unknown_occupied),
@@ -949,11 +884,9 @@ class Engine:
         Returns SURFACE_DTYPE records -- position in metres, unit normal into free space, probability, colour and
         weight of the nearer voxel -- of every sign change of the TSDF between two neighbouring voxels of at least
         min_weight, in block order (z, y, x), then voxel order within the block, then axis."""
-        p, n = C.c_void_p(), C.c_size_t()
         params = SurfaceParams(int(min_weight), float(min_prob), 0, 0)
-        _check(self.lib.fn["surface_points"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
-                                             C.byref(p), C.byref(n)), "surface_points")
-        return self._take(p, n.value, SURFACE_DTYPE)
+        return self._call_owned("surface_points", SURFACE_DTYPE, _box3(origin, "origin"), _box3(dims, "dims"),
+                                C.byref(params))
 
     def surface_points_device(self, origin, dims, d_points, capacity, d_count, min_weight=1, min_prob=0.0):
         """surface_points() into DEVICE buffers, asynchronous on the engine's stream: the first min(total, capacity)
@@ -961,27 +894,35 @@ class Engine:
         d_count.  d_points / d_count: a torch tensor, a devmem.DeviceArray or a raw pointer.  Returns the total (this
         waits for the stream)."""
         params = SurfaceParams(int(min_weight), float(min_prob), 0, 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_points, d_count)]
+        points, count = _device_ptrs(d_points, d_count)
         _check(self.lib.fn["surface_points_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
-                                                    C.byref(params), ptr[0] or None, int(capacity), ptr[1] or None),
+                                                    C.byref(params), points, int(capacity), count),
                "surface_points_device")
-        self.synchronize()
-        if hasattr(d_count, "cpu"):          # a torch tensor
-            return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
-        if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
-            return int(d_count.numpy().view(np.int64).reshape(-1)[0])
-        return None                          # a raw pointer: the caller reads it
+        total = self._read_back(d_count, np.int64)
+        return None if total is None else int(total[0])
+
+    def _mesh(self, symbol, origin, dims, params):
+        """surface_mesh() and cluster_mesh(): `symbol` with its params struct"""
+        pv, pt, nv, nt = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _check(self.lib.fn[symbol](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                   C.byref(pv), C.byref(nv), C.byref(pt), C.byref(nt)), symbol)
+        return self._take(pv, nv.value, SURFACE_DTYPE), self._take(pt, nt.value * 3, np.dtype("<i4")).reshape(-1, 3)
+
+    def _mesh_device(self, symbol, origin, dims, params, d_vertices, vertex_capacity, d_triangles, triangle_capacity,
+                     d_counts):
+        """surface_mesh_device() and cluster_mesh_device(): `symbol` with its params struct"""
+        vertices, triangles, counts = _device_ptrs(d_vertices, d_triangles, d_counts)
+        _check(self.lib.fn[symbol](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params), vertices,
+                                   int(vertex_capacity), triangles, int(triangle_capacity), counts), symbol)
+        totals = self._read_back(d_counts, np.int64, 2)
+        return None if totals is None else tuple(int(v) for v in totals)
 
     def surface_mesh(self, origin, dims, min_weight=1):
         """welded triangle mesh of a box of voxels (ratsdf_surface_mesh, include/ratsdf_surface_mesh.h): (vertices,
         triangles).  The vertices are SURFACE_DTYPE records, the surface points that the triangles of the box's
         complete cells use, each once, in surface_points' order; the triangles are int32 [n, 3] indices into them,
         wound so that their normal points into free space, in the order of their cell's voxel."""
-        pv, pt, nv, nt = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
-        params = SurfaceMeshParams(int(min_weight), 0, 0, 0)
-        _check(self.lib.fn["surface_mesh"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
-                                           C.byref(pv), C.byref(nv), C.byref(pt), C.byref(nt)), "surface_mesh")
-        return self._take(pv, nv.value, SURFACE_DTYPE), self._take(pt, nt.value * 3, np.dtype("<i4")).reshape(-1, 3)
+        return self._mesh("surface_mesh", origin, dims, SurfaceMeshParams(int(min_weight), 0, 0, 0))
 
     def surface_mesh_device(self, origin, dims, d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts,
                             min_weight=1):
@@ -990,18 +931,8 @@ class Engine:
         for a pure count), and the true totals as two int64 (vertices, triangles) to d_counts.  A triangle written
         while one of its vertices fell beyond vertex_capacity keeps its true index.  Each buffer: a torch tensor, a
         devmem.DeviceArray or a raw pointer.  Returns the two totals (this waits for the stream)."""
-        params = SurfaceMeshParams(int(min_weight), 0, 0, 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_vertices, d_triangles, d_counts)]
-        _check(self.lib.fn["surface_mesh_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
-                                                  C.byref(params), ptr[0] or None, int(vertex_capacity),
-                                                  ptr[1] or None, int(triangle_capacity), ptr[2] or None),
-               "surface_mesh_device")
-        self.synchronize()
-        if hasattr(d_counts, "cpu"):         # a torch tensor
-            return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])
-        if hasattr(d_counts, "numpy"):       # a devmem.DeviceArray
-            return tuple(int(v) for v in d_counts.numpy().view(np.int64).reshape(-1)[:2])
-        return None                          # a raw pointer: the caller reads it
+        return self._mesh_device("surface_mesh_device", origin, dims, SurfaceMeshParams(int(min_weight), 0, 0, 0),
+                                 d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts)
 
     def cluster_mesh(self, origin, dims, factor=4, min_weight=1):
         """clustered mesh of a box of voxels (ratsdf_cluster_mesh, include/ratsdf_cluster_mesh.h): (vertices,
@@ -1009,28 +940,15 @@ class Engine:
         voxels (factor 2, 4 or 8): one SURFACE_DTYPE record per non-empty cluster -- the mean of its members -- in
         block order, then cluster order within the block; the triangles are int32 [n, 3] indices into them, those with
         two vertices in one cluster dropped, the smallest index first, each once."""
-        pv, pt, nv, nt = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
-        params = ClusterMeshParams(int(min_weight), int(factor), 0, 0)
-        _check(self.lib.fn["cluster_mesh"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
-                                           C.byref(pv), C.byref(nv), C.byref(pt), C.byref(nt)), "cluster_mesh")
-        return self._take(pv, nv.value, SURFACE_DTYPE), self._take(pt, nt.value * 3, np.dtype("<i4")).reshape(-1, 3)
+        return self._mesh("cluster_mesh", origin, dims, ClusterMeshParams(int(min_weight), int(factor), 0, 0))
 
     def cluster_mesh_device(self, origin, dims, d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts,
                             factor=4, min_weight=1):
         """cluster_mesh() into DEVICE buffers, asynchronous on the engine's stream: the arguments, the capacity rule
         and the result of surface_mesh_device()."""
-        params = ClusterMeshParams(int(min_weight), int(factor), 0, 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_vertices, d_triangles, d_counts)]
-        _check(self.lib.fn["cluster_mesh_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"),
-                                                  C.byref(params), ptr[0] or None, int(vertex_capacity),
-                                                  ptr[1] or None, int(triangle_capacity), ptr[2] or None),
-               "cluster_mesh_device")
-        self.synchronize()
-        if hasattr(d_counts, "cpu"):         # a torch tensor
-            return tuple(int(v) for v in d_counts.cpu().numpy().view(np.int64).reshape(-1)[:2])
-        if hasattr(d_counts, "numpy"):       # a devmem.DeviceArray
-            return tuple(int(v) for v in d_counts.numpy().view(np.int64).reshape(-1)[:2])
-        return None                          # a raw pointer: the caller reads it
+        return self._mesh_device("cluster_mesh_device", origin, dims,
+                                 ClusterMeshParams(int(min_weight), int(factor), 0, 0), d_vertices, vertex_capacity,
+                                 d_triangles, triangle_capacity, d_counts)
 
     def regions(self, origin, dims, states=1 << ESDF_STATE_FREE, occupied_below=0.0, min_prob=0.0, with_labels=True):
         """connected regions of a box of voxels (ratsdf_regions, include/ratsdf_regions.h): the voxels whose
@@ -1040,15 +958,10 @@ class Engine:
         table is REGION_DTYPE records, one per region, ascending in root (size, voxels that border UNKNOWN ones, box
         faces reached, bounding box in absolute voxel indices).  Without with_labels only the table."""
         o, d = _box3(origin, "origin"), _box3(dims, "dims")
-        n = int(np.prod([int(v) for v in d], dtype=object))
-        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
-        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
-        labels = np.empty(shape, dtype=np.int32) if with_labels else None
+        labels = np.empty(_box_shape(d), dtype=np.int32) if with_labels else None
         params = RegionsParams(float(occupied_below), float(min_prob), int(states), 0)
-        p, m = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn["regions"](self._h, o, d, C.byref(params), labels.ctypes.data if with_labels else None,
-                                      C.byref(p), C.byref(m)), "regions")
-        table = self._take(p, m.value, REGION_DTYPE)
+        table = self._call_owned("regions", REGION_DTYPE, o, d, C.byref(params),
+                                 labels.ctypes.data if with_labels else None)
         return (labels, table) if with_labels else table
 
     def regions_device(self, origin, dims, d_labels, d_regions, capacity, d_count, states=1 << ESDF_STATE_FREE,
@@ -1058,16 +971,11 @@ class Engine:
         (16-byte aligned; 0 with capacity 0 for a pure count) and the total as an int64 to d_count.  Each buffer: a
         torch tensor, a devmem.DeviceArray or a raw pointer.  Returns the total (this waits for the stream)."""
         params = RegionsParams(float(occupied_below), float(min_prob), int(states), 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_labels, d_regions, d_count)]
+        labels, regions, count = _device_ptrs(d_labels, d_regions, d_count)
         _check(self.lib.fn["regions_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
-                                             ptr[0] or None, ptr[1] or None, int(capacity), ptr[2] or None),
-               "regions_device")
-        self.synchronize()
-        if hasattr(d_count, "cpu"):          # a torch tensor
-            return int(d_count.cpu().numpy().view(np.int64).reshape(-1)[0])
-        if hasattr(d_count, "numpy"):        # a devmem.DeviceArray
-            return int(d_count.numpy().view(np.int64).reshape(-1)[0])
-        return None                          # a raw pointer: the caller reads it
+                                             labels, regions, int(capacity), count), "regions_device")
+        total = self._read_back(d_count, np.int64)
+        return None if total is None else int(total[0])
 
     @staticmethod
     def _cost_flags(unknown_occupied, through_unknown, faces_only, resume=False):
@@ -1084,9 +992,7 @@ class Engine:
         COST_NONE where no goal is reached; with with_next the uint8 direction codes (COST_AT_GOAL, COST_NO_STEP or
         (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1): see descend()); summary a COST_SUMMARY_DTYPE record."""
         o, d = _box3(origin, "origin"), _box3(dims, "dims")
-        n = int(np.prod([int(v) for v in d], dtype=object))
-        # (a box beyond the limits gets a one-voxel placeholder: the library refuses it, status 1)
-        shape = tuple(int(v) for v in d[::-1]) if all(v > 0 for v in d) and n <= 1 << 27 else (1,)
+        shape = _box_shape(d)
         g = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 3))
         cost = np.empty(shape, dtype=np.uint32)
         nxt = np.empty(shape, dtype=np.uint8) if with_next else None
@@ -1109,37 +1015,39 @@ class Engine:
         tensor, a devmem.DeviceArray or a raw pointer.  Returns the summary record (this waits for the stream)."""
         params = CostParams(float(occupied_below), float(clearance),
                             self._cost_flags(unknown_occupied, through_unknown, faces_only, resume), int(rounds))
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_goals, d_cost, d_next, d_summary)]
+        goals, cost, nxt, summary = _device_ptrs(d_goals, d_cost, d_next, d_summary)
         _check(self.lib.fn["cost_to_go_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
-                                                ptr[0] or None, int(n_goals), ptr[1] or None, ptr[2] or None,
-                                                ptr[3] or None), "cost_to_go_device")
-        self.synchronize()
-        if hasattr(d_summary, "cpu"):        # a torch tensor
-            return d_summary.cpu().numpy().reshape(-1).view(np.uint8)[:32].view(COST_SUMMARY_DTYPE)[0]
-        if hasattr(d_summary, "numpy"):      # a devmem.DeviceArray
-            return d_summary.numpy().reshape(-1).view(np.uint8)[:32].view(COST_SUMMARY_DTYPE)[0]
-        return None                          # a raw pointer: the caller reads it
+                                                goals, int(n_goals), cost, nxt, summary), "cost_to_go_device")
+        record = self._read_back(d_summary, COST_SUMMARY_DTYPE)
+        return None if record is None else record[0]
 
     def label_set(self, points, labels, cell=0.0):
         """a LabelSet of n labelled points (ratsdf_labelset_create, include/ratsdf_score.h): points [n, 3] float32
         metres, labels [n] uint8 of LABEL_IGNORE / LABEL_LOW / LABEL_HIGH.  cell: the edge of the search grid's cells,
         0 for 8 voxel sizes of this engine.  With `points` and `labels` on the device (torch tensors or
         devmem.DeviceArray: float32 [n, 3] and uint8 [n], contiguous) it is built from them in place."""
+        return self._labelled(LabelSet, "point", cell, (points, np.float32, (-1, 3)), (labels, np.uint8, (-1,)))
+
+    def _labelled(self, cls, what, cell, xyz, *more):
+        """label_set() and label_mesh(): a `cls` from (array, dtype, shape) triples, the positions first, then every
+        further array, which goes to the library as a (pointer, items) pair.  Arrays on the device -- the positions
+        have a data_ptr() -- are taken in place, others as contiguous host arrays of that dtype and shape."""
         h = C.c_void_p()
-        if hasattr(points, "data_ptr"):
-            n = int(labels.shape[0]) if hasattr(labels, "shape") else int(len(labels))
-            _check(self.lib.fn["labelset_create_device"](self._h, points.data_ptr() or None, labels.data_ptr() or None,
-                                                         n, C.c_float(float(cell)), C.byref(h)),
-                   "labelset_create_device")
-            return LabelSet(self.lib, h)
-        xyz = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
-        if lab.shape[0] != xyz.shape[0]:
-            raise ValueError("one label per point")
-        _check(self.lib.fn["labelset_create"](self._h, xyz.ctypes.data if len(xyz) else None,
-                                              lab.ctypes.data if len(lab) else None, len(xyz), C.c_float(float(cell)),
-                                              C.byref(h)), "labelset_create")
-        return LabelSet(self.lib, h)
+        if hasattr(xyz[0], "data_ptr"):
+            symbol = cls._prefix + "_create_device"
+            arrays = [a for a, _, _ in (xyz,) + more]
+            counts = [int(a.shape[0]) if hasattr(a, "shape") else int(len(a)) for a in arrays[1:]]
+            ptrs = [a.data_ptr() or None for a in arrays]
+        else:
+            symbol = cls._prefix + "_create"
+            arrays = [np.ascontiguousarray(a, dtype=dtype).reshape(shape) for a, dtype, shape in (xyz,) + more]
+            if arrays[1].shape[0] != arrays[0].shape[0]:
+                raise ValueError(f"one label per {what}")
+            counts = [len(a) for a in arrays[1:]]
+            ptrs = [a.ctypes.data if len(a) else None for a in arrays]
+        pairs = [v for pair in zip(ptrs[1:], counts) for v in pair]
+        _check(self.lib.fn[symbol](self._h, ptrs[0], *pairs, C.c_float(float(cell)), C.byref(h)), symbol)
+        return cls(self.lib, h)
 
     def score_labels(self, label_set, tsdf_below=0.1, max_dist=None, p_cutoff=0.5, min_weight=0, per_voxel=False):
         """the map scored against a LabelSet (ratsdf_score_labels): every voxel with |tsdf| < tsdf_below and weight >=
@@ -1163,11 +1071,9 @@ class Engine:
             max_dist = 4.0 * labelled.info["cell"]
         params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
         rec = np.zeros((), dtype=LABEL_SCORE_DTYPE)
-        p, m = C.c_void_p(), C.c_size_t()
-        _check(self.lib.fn[symbol](self._h, labelled._h, C.byref(params), rec.ctypes.data,
-                                   C.byref(p) if per_voxel else None, C.byref(m) if per_voxel else None), symbol)
-        score = LabelScore(rec)
-        return (score, self._take(p, m.value, VOXEL_LABEL_DTYPE)) if per_voxel else score
+        records = self._call_owned(symbol, VOXEL_LABEL_DTYPE, labelled._h, C.byref(params), rec.ctypes.data,
+                                   wanted=per_voxel)
+        return (LabelScore(rec), records) if per_voxel else LabelScore(rec)
 
     def _score_device(self, symbol, labelled, d_score, d_per_voxel, capacity, d_count, tsdf_below, max_dist, p_cutoff,
                       min_weight):
@@ -1175,9 +1081,8 @@ class Engine:
         if max_dist is None:
             max_dist = 4.0 * labelled.info["cell"]
         params = ScoreParams(float(tsdf_below), float(max_dist), float(p_cutoff), int(min_weight), 0)
-        ptr = [v.data_ptr() if hasattr(v, "data_ptr") else int(v or 0) for v in (d_score, d_per_voxel, d_count)]
-        _check(self.lib.fn[symbol](self._h, labelled._h, C.byref(params), ptr[0] or None, ptr[1] or None,
-                                   int(capacity), ptr[2] or None), symbol)
+        score, records, count = _device_ptrs(d_score, d_per_voxel, d_count)
+        _check(self.lib.fn[symbol](self._h, labelled._h, C.byref(params), score, records, int(capacity), count), symbol)
 
     def label_mesh(self, vertices, labels, triangles, cell=0.0):
         """a LabelMesh (ratsdf_labelmesh_create, include/ratsdf_score_mesh.h): vertices [n, 3] float32 metres, labels
@@ -1185,25 +1090,8 @@ class Engine:
         the label of its first vertex.  cell: the edge of the search grid's cells, 0 for 8 voxel sizes of this engine.
         With the three arrays on the device (torch tensors or devmem.DeviceArray: float32 [n, 3], uint8 [n] and
         int32 [m, 3], contiguous) it is built from them in place."""
-        h = C.c_void_p()
-        if hasattr(vertices, "data_ptr"):
-            n = int(labels.shape[0]) if hasattr(labels, "shape") else int(len(labels))
-            m = int(triangles.shape[0]) if hasattr(triangles, "shape") else int(len(triangles))
-            _check(self.lib.fn["labelmesh_create_device"](self._h, vertices.data_ptr() or None,
-                                                          labels.data_ptr() or None, n, triangles.data_ptr() or None,
-                                                          m, C.c_float(float(cell)), C.byref(h)),
-                   "labelmesh_create_device")
-            return LabelMesh(self.lib, h)
-        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
-        lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
-        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-        if lab.shape[0] != xyz.shape[0]:
-            raise ValueError("one label per vertex")
-        _check(self.lib.fn["labelmesh_create"](self._h, xyz.ctypes.data if len(xyz) else None,
-                                               lab.ctypes.data if len(lab) else None, len(xyz),
-                                               tri.ctypes.data if len(tri) else None, len(tri),
-                                               C.c_float(float(cell)), C.byref(h)), "labelmesh_create")
-        return LabelMesh(self.lib, h)
+        return self._labelled(LabelMesh, "vertex", cell, (vertices, np.float32, (-1, 3)), (labels, np.uint8, (-1,)),
+                              (triangles, np.int32, (-1, 3)))
 
     def score_mesh(self, label_mesh, tsdf_below=0.1, max_dist=None, p_cutoff=0.5, min_weight=0, per_voxel=False):
         """the map scored against a LabelMesh (ratsdf_score_mesh): every voxel with |tsdf| < tsdf_below and weight >=
