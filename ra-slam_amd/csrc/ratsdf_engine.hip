@@ -28,6 +28,7 @@
 #include "kernels_cluster_mesh.h"
 #include "kernels_regions.h"
 #include "kernels_cost.h"
+#include "kernels_exposure.h"
 #include "kernels_score.h"
 #include "kernels_score_mesh.h"
 #include "kernels_fuse.h"
@@ -269,6 +270,7 @@ struct EngineMem {
   Workspace ws_cluster_mesh;  // ratsdf_cluster_mesh*: cluster_mesh_layout, per cell of the block grid
   Workspace ws_regions;       // ratsdf_regions*: regions_layout, per voxel
   Workspace ws_cost;          // ratsdf_cost_to_go*: cost_layout, per voxel (an ESDF workspace of its own inside)
+  Workspace ws_exposure;      // ratsdf_exposure*: exposure_layout, per voxel
   Workspace ws_score;         // ratsdf_score_labels and ratsdf_score_mesh: score_layout, one item
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
@@ -2083,3 +2085,4 @@ const char* ratsdf_backend(void) { return "hip-gfx950"; }
 #include "cost.inc"     // ratsdf_cost_to_go[_device] (include/ratsdf_cost.h)
 #include "score.inc"    // ratsdf_labelset_* / ratsdf_score_labels[_device] (include/ratsdf_score.h)
 #include "score_mesh.inc"  // ratsdf_labelmesh_* / ratsdf_score_mesh[_device] (include/ratsdf_score_mesh.h)
+#include "exposure.inc"  // ratsdf_exposure[_device] (include/ratsdf_surface.h)

@@ -1,4 +1,4 @@
-// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc, cost.inc) and the label
+// workspace.h -- how the box read-outs (esdf.inc, surface.inc, surface_mesh.inc, regions.inc, cost.inc, exposure.inc) and the label
 // scores (score.inc) carve their device workspaces: a cursor that walks a buffer part by part, and one layout function per read-out that fills its *Work
 // struct from a cursor.  Walked from a null base the same function yields the buffer's size (ws_bytes), so a layout is
 // written once and cannot disagree with the allocation.  Plain C++, no HIP types: tests/cpp/test_workspace_layout.cc
@@ -146,6 +146,31 @@ inline void cost_layout(WsCursor& c, size_t n, CostWork* w) {
   w->dirty = c.take<uint32_t>(8 * cost_tiles_max(n));
   w->summary = c.take_raw<uint32_t>(32);
   w->counts = c.take_raw<uint32_t>(ws_round(40) - 32);
+}
+
+// exposure (exposure.inc), a box of n voxels, a buffer of its own: state bytes (n B) | the blocking bitmap, a 64-bit
+// word per 4 x 4 x 4 brick | the lamps' voxels and acceptance (64 x 16 B) | the host entry point's lamp table
+// (64 x 16 B) | its summary (32 B), rounded.
+// exposure_bricks_max(n): no box of n voxels has more bricks -- ceil(X/4) ceil(Y/4) ceil(Z/4) <= (X+3)(Y+3)(Z+3) / 64 =
+// (n + 3 (XY + YZ + XZ) + 9 (X + Y + Z) + 27) / 64, where each pair product is <= n and <= 2^20 (every axis <= 1024),
+// their sum <= 2n + 1 (at its largest when two axes are 1) and X + Y + Z <= 3072.  Monotonic in n: a layout for the
+// buffer's capacity holds every smaller box.
+inline size_t exposure_bricks_max(size_t n) {
+  const size_t pairs = 2 * n + 1 < ((size_t)3 << 20) ? 2 * n + 1 : (size_t)3 << 20;
+  return (n + 3 * pairs + 9 * 3072 + 27) / 64 + 1;
+}
+struct ExposureWork {
+  uint8_t* st;
+  unsigned long long* bits;
+  int32_t* lamp_vox;
+  uint32_t *table, *summary;
+};
+inline void exposure_layout(WsCursor& c, size_t n, ExposureWork* w) {
+  w->st = c.take<uint8_t>(n);
+  w->bits = c.take<unsigned long long>(8 * exposure_bricks_max(n));
+  w->lamp_vox = c.take_raw<int32_t>(1024);
+  w->table = c.take_raw<uint32_t>(1024);
+  w->summary = c.take<uint32_t>(32);
 }
 
 // label score against points and against a mesh (score_host in score.inc serves both, from one buffer), n = 1: the

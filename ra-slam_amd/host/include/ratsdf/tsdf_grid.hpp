@@ -23,7 +23,7 @@ namespace ratsdf {
   X(raycast, 1) X(gather_valid_mesh, 1) X(download_all_mesh, 1) X(free_buffer, 1) X(num_active_blocks, 1)            \
   X(status_string, 1) X(backend, 1)                                                                                  \
   X(save_map, 0) X(load_map, 0) X(map_file_info, 0) X(sample_points, 0) X(esdf, 0) X(surface_points, 0)              \
-  X(surface_mesh, 0) X(cluster_mesh, 0) X(regions, 0) X(cost_to_go, 0)                                               \
+  X(surface_mesh, 0) X(cluster_mesh, 0) X(regions, 0) X(cost_to_go, 0) X(exposure, 0)                                \
   X(labelset_create, 0) X(labelset_info_get, 0) X(labelset_destroy, 0) X(score_labels, 0)                            \
   X(labelmesh_create, 0) X(labelmesh_info_get, 0) X(labelmesh_destroy, 0) X(score_mesh, 0)                           \
   X(fuse_map, 0) X(fuse_blocks, 0) X(fuse_map_file, 0) X(fuse_map_transformed, 0) X(fuse_map_coarsened, 0)
@@ -171,6 +171,16 @@ class TSDFGrid {
   int CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params, const int32_t* goals,
                int32_t n_goals, std::vector<uint32_t>* cost, std::vector<uint8_t>* next,
                ratsdf_cost_summary* summary);
+  // exposure of surface points to lamps through a box of voxels (include/ratsdf_surface.h, ratsdf_exposure): which of
+  // the n_lamps lamps light each of the n_points points, and the summed irradiance.  *dose is in/out: with
+  // RATSDF_EXPOSURE_ACCUMULATE it must hold n_points floats and the sums go on from them, without the flag it is
+  // replaced by n_points zeros first; *mask and *lamp_table (each may be nullptr) receive n_points words and n_lamps
+  // records, *summary (may be nullptr) the summary.  Returns the status (also kept in last_status()); the vectors are
+  // empty unless it is RATSDF_OK.  No reference counterpart.
+  int Exposure(const int32_t origin[3], const int32_t dims[3], const ratsdf_exposure_params& params,
+               const ratsdf_surface_point* points, int64_t n_points, const ratsdf_lamp* lamps, int32_t n_lamps,
+               std::vector<float>* dose, std::vector<uint64_t>* mask, std::vector<ratsdf_lamp_record>* lamp_table,
+               ratsdf_exposure_summary* summary);
   // the map scored against labelled points (include/ratsdf_score.h).  MakeLabelSet: n points (xyz: 3 floats each,
   // metres) with a label each (RATSDF_LABEL_*) into *out (what it held is destroyed first); cell: the edge of the
   // search grid, 0 for 8 voxel sizes.  ScoreLabels: every voxel that params selects takes the label of its nearest

@@ -178,6 +178,11 @@ class TSDFSystem {
   int CostToGo(const int32_t origin[3], const int32_t dims[3], const ratsdf_cost_params& params, const int32_t* goals,
                int32_t n_goals, std::vector<uint32_t>* cost, std::vector<uint8_t>* next,
                ratsdf_cost_summary* summary);
+  // TSDFGrid::Exposure under the engine's mutex, like ESDF
+  int Exposure(const int32_t origin[3], const int32_t dims[3], const ratsdf_exposure_params& params,
+               const ratsdf_surface_point* points, int64_t n_points, const ratsdf_lamp* lamps, int32_t n_lamps,
+               std::vector<float>* dose, std::vector<uint64_t>* mask, std::vector<ratsdf_lamp_record>* lamp_table,
+               ratsdf_exposure_summary* summary);
   // TSDFGrid::MakeLabelSet / TSDFGrid::ScoreLabels under the engine's mutex, like ESDF
   int MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out);
   int ScoreLabels(const LabelSet& set, const ratsdf_score_params& params, ratsdf_label_score* out,

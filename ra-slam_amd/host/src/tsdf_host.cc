@@ -290,6 +290,38 @@ int TSDFGrid::CostToGo(const int32_t origin[3], const int32_t dims[3], const rat
   return status_;
 }
 
+int TSDFGrid::Exposure(const int32_t origin[3], const int32_t dims[3], const ratsdf_exposure_params& params,
+                       const ratsdf_surface_point* points, int64_t n_points, const ratsdf_lamp* lamps, int32_t n_lamps,
+                       std::vector<float>* dose, std::vector<uint64_t>* mask,
+                       std::vector<ratsdf_lamp_record>* lamp_table, ratsdf_exposure_summary* summary) {
+  if (mask) mask->clear();
+  if (lamp_table) lamp_table->clear();
+  const bool counts_ok = n_points >= 0 && n_points <= ((int64_t)1 << 24) && n_lamps >= 0 &&
+                         n_lamps <= RATSDF_EXPOSURE_MAX_LAMPS;
+  const bool accumulate = (params.flags & RATSDF_EXPOSURE_ACCUMULATE) != 0u;
+  if (!engine_ || !dose || !counts_ok || (accumulate && dose->size() != (size_t)n_points)) {
+    if (dose) dose->clear();
+    return status_ = RATSDF_ERR_BAD_ARGUMENT;
+  }
+  if (!accumulate) dose->assign((size_t)n_points, 0.0f);
+  if (mask) mask->resize((size_t)n_points);
+  if (lamp_table) lamp_table->resize((size_t)n_lamps);
+  float none = 0.0f;  // (an empty vector's data() may be null: no points, nothing written)
+  ratsdf_exposure_summary s;
+  memset(&s, 0, sizeof(s));
+  call("Exposure", api_->exposure, origin, dims, &params, points, n_points, lamps, n_lamps,
+       n_points ? dose->data() : &none, mask && n_points ? mask->data() : nullptr,
+       lamp_table && n_lamps ? lamp_table->data() : nullptr, &s);
+  if (status_ != RATSDF_OK) {
+    dose->clear();
+    if (mask) mask->clear();
+    if (lamp_table) lamp_table->clear();
+  } else if (summary) {
+    *summary = s;
+  }
+  return status_;
+}
+
 template <class Labelled, class F, class... Args>
 int TSDFGrid::make_labelled(const char* what, Labelled* out, F f, Args... args) {
   if (out) out->reset();
@@ -640,6 +672,15 @@ int TSDFSystem::CostToGo(const int32_t origin[3], const int32_t dims[3], const r
                          const int32_t* goals, int32_t n_goals, std::vector<uint32_t>* cost,
                          std::vector<uint8_t>* next, ratsdf_cost_summary* summary) {
   return read([&](TSDFGrid& g) { return g.CostToGo(origin, dims, params, goals, n_goals, cost, next, summary); });
+}
+
+int TSDFSystem::Exposure(const int32_t origin[3], const int32_t dims[3], const ratsdf_exposure_params& params,
+                         const ratsdf_surface_point* points, int64_t n_points, const ratsdf_lamp* lamps,
+                         int32_t n_lamps, std::vector<float>* dose, std::vector<uint64_t>* mask,
+                         std::vector<ratsdf_lamp_record>* lamp_table, ratsdf_exposure_summary* summary) {
+  return read([&](TSDFGrid& g) {
+    return g.Exposure(origin, dims, params, points, n_points, lamps, n_lamps, dose, mask, lamp_table, summary);
+  });
 }
 
 int TSDFSystem::MakeLabelSet(const float* xyz, const uint8_t* labels, size_t n, float cell, LabelSet* out) {

@@ -16,6 +16,8 @@ from ._abi import LabelMesh, LabelMeshInfo
 from ._abi import ClusterMeshParams
 from ._abi import (COST_AT_GOAL, COST_CONTINUE, COST_FACES_ONLY, COST_NO_STEP, COST_NONE, COST_SUMMARY_DTYPE,
                    COST_THROUGH_UNKNOWN, COST_UNKNOWN_OCCUPIED, CostParams, cost_direction, descend)
+from ._abi import (EXPOSURE_ACCUMULATE, EXPOSURE_MAX_LAMPS, EXPOSURE_SUMMARY_DTYPE, EXPOSURE_UNKNOWN_OCCUPIED, LAMP_DTYPE,
+                   LAMP_RECORD_DTYPE, ExposureParams)
 from .pose import compose, identity_pose, invert, pose_from_matrix
 
 _PKG_ROOT = Path(__file__).resolve().parent.parent
@@ -58,4 +60,5 @@ __all__ = ["TSDFGrid", "Engine", "Group", "Library", "library", "Intrinsics", "P
            "LabelSet", "LabelScore", "LABEL_IGNORE", "LABEL_LOW", "LABEL_HIGH", "LabelMesh", "LabelMeshInfo",
            "ClusterMeshParams", "CostParams", "COST_SUMMARY_DTYPE", "COST_NONE", "COST_AT_GOAL", "COST_NO_STEP",
            "COST_UNKNOWN_OCCUPIED", "COST_THROUGH_UNKNOWN", "COST_FACES_ONLY", "COST_CONTINUE",
-           "cost_direction", "descend"]
+           "cost_direction", "descend", "ExposureParams", "LAMP_DTYPE", "LAMP_RECORD_DTYPE",
+           "EXPOSURE_SUMMARY_DTYPE", "EXPOSURE_UNKNOWN_OCCUPIED", "EXPOSURE_ACCUMULATE", "EXPOSURE_MAX_LAMPS"]

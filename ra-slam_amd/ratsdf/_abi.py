@@ -90,6 +90,23 @@ class SurfaceParams(C.Structure):
     _fields_ = [("min_weight", C.c_int32), ("min_prob", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# ... and the exposure of such points to lamps (ratsdf_exposure*): ratsdf_lamp (16 bytes), ratsdf_lamp_record (16 bytes),
+# ratsdf_exposure_summary (32 bytes)
+EXPOSURE_UNKNOWN_OCCUPIED, EXPOSURE_ACCUMULATE = 1, 2
+EXPOSURE_MAX_LAMPS = 64
+LAMP_DTYPE = np.dtype([("pos", "<f4", (3,)), ("power", "<f4")])
+LAMP_RECORD_DTYPE = np.dtype([("accepted", "<i4"), ("lit", "<i4"), ("lit_high", "<i4"), ("reserved", "<i4")])
+EXPOSURE_SUMMARY_DTYPE = np.dtype([("lit_pairs", "<i8"), ("points_lit", "<i4"), ("points_outside", "<i4"),
+                                   ("lamps_accepted", "<i4"), ("reserved", "<u4", (3,))])
+assert LAMP_DTYPE.itemsize == 16 and LAMP_RECORD_DTYPE.itemsize == 16 and EXPOSURE_SUMMARY_DTYPE.itemsize == 32
+
+
+class ExposureParams(C.Structure):
+    """ratsdf_exposure_params"""
+    _fields_ = [("occupied_below", C.c_float), ("max_range", C.c_float), ("min_irradiance", C.c_float),
+                ("p_cutoff", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class SurfaceMeshParams(C.Structure):
     """ratsdf_surface_mesh_params (include/ratsdf_surface_mesh.h: welded triangle mesh of a box)"""
     _fields_ = [("min_weight", C.c_int32), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
@@ -415,6 +432,8 @@ ABI = {
     "ratsdf_surface.h": {
         "surface_points": _box + [_P(SurfaceParams)] + _owned,
         "surface_points_device": _box + [_P(SurfaceParams), _vp, _i64, _vp],
+        "exposure": _box + [_P(ExposureParams), _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+        "exposure_device": _box + [_P(ExposureParams), _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     },
     "ratsdf_surface_mesh.h": {
         "surface_mesh": _box + [_P(SurfaceMeshParams)] + _mesh,
@@ -900,6 +919,81 @@ class Engine:
                "surface_points_device")
         total = self._read_back(d_count, np.int64)
         return None if total is None else int(total[0])
+
+    @staticmethod
+    def _exposure_params(occupied_below, max_range, min_irradiance, p_cutoff, unknown_occupied, accumulate):
+        flags = (EXPOSURE_UNKNOWN_OCCUPIED if unknown_occupied else 0) | (EXPOSURE_ACCUMULATE if accumulate else 0)
+        return ExposureParams(float(occupied_below), float(max_range), float(min_irradiance), float(p_cutoff), flags,
+                              (C.c_uint32 * 3)(0, 0, 0))
+
+    def exposure(self, origin, dims, points, lamps, occupied_below=0.0, max_range=np.inf, min_irradiance=0.0,
+                 p_cutoff=0.5, unknown_occupied=False, dose=None, with_mask=False):
+        """exposure of surface points to lamps through a box of voxels (ratsdf_exposure, include/ratsdf_surface.h):
+        `points` SURFACE_DTYPE records (surface_points' output), `lamps` LAMP_DTYPE records (at most
+        EXPOSURE_MAX_LAMPS: position in metres, power).  A lamp lights a point that faces it, within max_range, when
+        the integer voxel walk from the point's start voxel (one voxel along its normal) to the lamp's voxel meets no
+        OCCUPIED voxel of the box (nor an UNKNOWN one with unknown_occupied).  Returns (dose, [mask,] table, summary):
+        dose float32 [n], the sum of P cos(theta) / 4 pi r^2 over the visible lamps in ascending lamp order -- on top
+        of `dose` when one is given (the chain for more than 64 lamps), else from 0; mask uint64 [n], bit k for lamp k;
+        table LAMP_RECORD_DTYPE [n_lamps] (accepted, points lit with at least min_irradiance, those of them with
+        prob >= p_cutoff); summary an EXPOSURE_SUMMARY_DTYPE record."""
+        o, d = _box3(origin, "origin"), _box3(dims, "dims")
+        pts = np.ascontiguousarray(np.asarray(points, dtype=SURFACE_DTYPE).reshape(-1))
+        lmp = np.ascontiguousarray(np.asarray(lamps, dtype=LAMP_DTYPE).reshape(-1))
+        out = np.zeros(max(len(pts), 1), dtype=np.float32)[:len(pts)]   # (never a null pointer: an empty list too)
+        if dose is not None:
+            if np.size(dose) != len(pts):
+                raise ValueError("dose must hold one float per point")
+            out[:] = np.asarray(dose, dtype=np.float32).reshape(-1)
+        mask = np.zeros(len(pts), dtype=np.uint64) if with_mask else None
+        table = np.zeros(len(lmp), dtype=LAMP_RECORD_DTYPE)
+        summary = np.zeros(1, dtype=EXPOSURE_SUMMARY_DTYPE)
+        params = self._exposure_params(occupied_below, max_range, min_irradiance, p_cutoff, unknown_occupied,
+                                       dose is not None)
+        _check(self.lib.fn["exposure"](self._h, o, d, C.byref(params), pts.ctypes.data if len(pts) else None, len(pts),
+                                       lmp.ctypes.data if len(lmp) else None, len(lmp),
+                                       out.ctypes.data,
+                                       mask.ctypes.data if with_mask and len(pts) else None,
+                                       table.ctypes.data if len(lmp) else None, summary.ctypes.data), "exposure")
+        return (out, mask, table, summary[0]) if with_mask else (out, table, summary[0])
+
+    def exposure_device(self, origin, dims, d_points, n_points, d_lamps, n_lamps, d_dose, d_mask, d_lamp_table,
+                        d_summary, occupied_below=0.0, max_range=np.inf, min_irradiance=0.0, p_cutoff=0.5,
+                        unknown_occupied=False, accumulate=False):
+        """exposure() on DEVICE buffers, asynchronous on the engine's stream: n_points 32-byte records at d_points and
+        n_lamps 16-byte records at d_lamps (16-byte aligned); the doses to d_dose (float32, in/out with accumulate),
+        the masks to d_mask (uint64, 0 for none), the lamp table to d_lamp_table (n_lamps 16-byte records, 0 for none)
+        and the 32-byte summary to d_summary (8-byte aligned).  Each buffer: a torch tensor, a devmem.DeviceArray or a
+        raw pointer.  Returns the summary record (this waits for the stream)."""
+        params = self._exposure_params(occupied_below, max_range, min_irradiance, p_cutoff, unknown_occupied,
+                                       accumulate)
+        points, lamps, dose, mask, table, summary = _device_ptrs(d_points, d_lamps, d_dose, d_mask, d_lamp_table,
+                                                                 d_summary)
+        _check(self.lib.fn["exposure_device"](self._h, _box3(origin, "origin"), _box3(dims, "dims"), C.byref(params),
+                                              points, int(n_points), lamps, int(n_lamps), dose, mask, table, summary),
+               "exposure_device")
+        record = self._read_back(d_summary, EXPOSURE_SUMMARY_DTYPE)
+        return None if record is None else record[0]
+
+    def surface_exposure(self, origin, dims, lamps, min_weight=1, min_prob=0.0, **exposure_kw):
+        """surface_points_device() and then exposure_device() of the same box, the points staying on the device in
+        between: (points, dose, mask) as numpy arrays -- SURFACE_DTYPE records, float32, uint64 -- plus the lamp table
+        and the summary record.  exposure_kw: exposure_device's keywords but accumulate."""
+        from .devmem import DeviceArray
+        dev = self.device
+        lmp = np.ascontiguousarray(np.asarray(lamps, dtype=LAMP_DTYPE).reshape(-1))
+        d_count = DeviceArray(np.zeros(1, dtype=np.int64), dev)
+        n = self.surface_points_device(origin, dims, 0, 0, d_count, min_weight=min_weight, min_prob=min_prob)
+        d_points = DeviceArray(np.zeros(max(n, 1), dtype=SURFACE_DTYPE), dev)
+        self.surface_points_device(origin, dims, d_points, n, d_count, min_weight=min_weight, min_prob=min_prob)
+        d_lamps = DeviceArray(lmp if len(lmp) else np.zeros(1, dtype=LAMP_DTYPE), dev)
+        d_dose = DeviceArray(np.zeros(max(n, 1), dtype=np.float32), dev)   # (OUTSIDE points keep it: a defined 0)
+        d_mask = DeviceArray(np.zeros(max(n, 1), dtype=np.uint64), dev)
+        d_table = DeviceArray(np.zeros(max(len(lmp), 1), dtype=LAMP_RECORD_DTYPE), dev)
+        d_summary = DeviceArray(np.zeros(1, dtype=EXPOSURE_SUMMARY_DTYPE), dev)
+        summary = self.exposure_device(origin, dims, d_points if n else 0, n, d_lamps if len(lmp) else 0, len(lmp),
+                                       d_dose, d_mask, d_table if len(lmp) else 0, d_summary, **exposure_kw)
+        return (d_points.numpy()[:n], d_dose.numpy()[:n], d_mask.numpy()[:n], d_table.numpy()[:len(lmp)], summary)
 
     def _mesh(self, symbol, origin, dims, params):
         """surface_mesh() and cluster_mesh(): `symbol` with its params struct"""
