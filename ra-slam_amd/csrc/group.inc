@@ -10,31 +10,21 @@ struct ratsdf_group {
   int device = 0;
   int S = 0;
   std::vector<ratsdf_engine*> eng;
-  hipStream_t stream = nullptr;
-  std::vector<hipEvent_t> ev_member;  // member stream -> group stream
-  hipEvent_t ev_done = nullptr;       // group stream -> member streams
-  DevMem d_engs, d_jobs;  // EngineDev[S]; FrameJob[frames of a batch x S], grown on demand
-  // page-locked staging of the tables, two of each, used alternately (a copy may still be pending
-  // when the next batch is being prepared)
-  HostMem h_engs[2], h_jobs[2];
-  hipEvent_t ev_stage[2] = {nullptr, nullptr};
-  unsigned batch_no = 0;
   int split_a = 100, split_b = 0;  // look-ahead share of k_front / k_alloc_rank (rest: k_integrate)
+  // What the group owns leaves in the reverse of these declarations, behind the drain of its stream: the device
+  // tables, their page-locked staging, the events, the timer's events, the stream.
+  HipStream stream;
   KernelTimer timer;  // (mode 1: every fourth frame)
+  HipEvent ev_done;                 // group stream -> member streams
+  std::vector<HipEvent> ev_member;  // member stream -> group stream
+  // page-locked staging of both tables, EngineDev[S] | FrameJob[frames of a batch x S]: two sides used alternately (a
+  // copy may still be pending when the next batch is being prepared), one event per side behind both copies
+  TwinTable tables;
+  DevMem d_engs, d_jobs;  // EngineDev[S]; FrameJob[frames of a batch x S], grown on demand
+  size_t jobs_off() const { return ((size_t)S * sizeof(EngineDev) + 255) & ~(size_t)255; }
 
-  void free_all() {
+  ~ratsdf_group() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (DevMem* m : {&d_engs, &d_jobs}) m->reset();
-    for (int i = 0; i < 2; ++i) {
-      h_engs[i].reset();
-      h_jobs[i].reset();
-      if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
-    }
-    for (auto& ev : ev_member)
-      if (ev) (void)hipEventDestroy(ev);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    timer.destroy();
-    if (stream) (void)hipStreamDestroy(stream);
   }
 };
 
@@ -60,7 +50,7 @@ int ratsdf_group_create(ratsdf_engine* const* engines, int n, ratsdf_group** out
   g->device = engines[0]->device;
   g->S = n;
   g->eng.assign(engines, engines + n);
-  g->ev_member.assign((size_t)n, nullptr);
+  g->ev_member.resize((size_t)n);
 #ifdef RATSDF_STAMPS
   if (const char* v = getenv("RATSDF_GROUP_SPLIT")) {  // "a[,b]" like RATSDF_CAND_SPLIT
     const int x = atoi(v);
@@ -78,20 +68,15 @@ int ratsdf_group_create(ratsdf_engine* const* engines, int n, ratsdf_group** out
   do {                                                                   \
     if ((expr) != hipSuccess) {                                          \
       fprintf(stderr, "[ratsdf] group create failed: %s\n", #expr);      \
-      g->free_all();                                                     \
       delete g;                                                          \
       return RATSDF_ERR_DEVICE;                                          \
     }                                                                    \
   } while (0)
-  GROUP_CHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+  GROUP_CHK(g->stream.create(hipStreamNonBlocking));
   GROUP_CHK(g->d_engs.alloc((size_t)n * sizeof(EngineDev)));
-  for (int i = 0; i < 2; ++i) {
-    GROUP_CHK(g->h_engs[i].alloc((size_t)n * sizeof(EngineDev)));
-    GROUP_CHK(hipEventCreateWithFlags(&g->ev_stage[i], hipEventDisableTiming));
-  }
-  for (int i = 0; i < n; ++i)
-    GROUP_CHK(hipEventCreateWithFlags(&g->ev_member[(size_t)i], hipEventDisableTiming));
-  GROUP_CHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
+  GROUP_CHK(g->tables.grow(g->jobs_off()));
+  for (HipEvent& ev : g->ev_member) GROUP_CHK(ev.create(hipEventDisableTiming));
+  GROUP_CHK(g->ev_done.create(hipEventDisableTiming));
 #undef GROUP_CHK
   *out = g;
   return RATSDF_OK;
@@ -99,7 +84,6 @@ int ratsdf_group_create(ratsdf_engine* const* engines, int n, ratsdf_group** out
 
 int ratsdf_group_destroy(ratsdf_group* g) {
   ENTRY(g, true);
-  g->free_all();
   delete g;
   return RATSDF_OK;
 }
@@ -132,19 +116,20 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
     STCHK(e->ensure_image(npix, npix * (size_t)e->S));
   }
   // ---- tables ----
-  const unsigned slot = g->batch_no++ & 1u;
   const size_t njobs = (size_t)n * S;
-  const size_t job_bytes = njobs * sizeof(FrameJob);
-  if (job_bytes > g->d_jobs.size() || job_bytes > g->h_jobs[0].size() || job_bytes > g->h_jobs[1].size()) {
+  const size_t job_bytes = njobs * sizeof(FrameJob), jobs_off = g->jobs_off();
+  if (job_bytes > g->d_jobs.size() || jobs_off + job_bytes > g->tables.size()) {
     HIPCHK(hipStreamSynchronize(g->stream));
     STCHK(g->d_jobs.grow(job_bytes));
-    for (int i = 0; i < 2; ++i) STCHK(g->h_jobs[i].grow(job_bytes));
+    STCHK(g->tables.grow(jobs_off + job_bytes));
   }
   FrameJob* const d_jobs = g->d_jobs.as<FrameJob>();
   EngineDev* const d_engs = g->d_engs.as<EngineDev>();
-  HIPCHK(hipEventSynchronize(g->ev_stage[slot]));  // the copy that last used this staging pair is done
-  for (int s = 0; s < S; ++s) g->h_engs[slot].as<EngineDev>()[s] = g->eng[(size_t)s]->record();
-  FrameJob* hj = g->h_jobs[slot].as<FrameJob>();
+  void* side = nullptr;
+  STCHK(g->tables.acquire(&side));  // (the copies that last used this side are done)
+  EngineDev* he = static_cast<EngineDev*>(side);
+  for (int s = 0; s < S; ++s) he[s] = g->eng[(size_t)s]->record();
+  FrameJob* hj = reinterpret_cast<FrameJob*>(static_cast<uint8_t*>(side) + jobs_off);
   for (int f = 0; f < n; ++f)
     for (int s = 0; s < S; ++s) {
       const size_t i = (size_t)f * S + s;
@@ -157,10 +142,8 @@ int ratsdf_group_integrate_device_batch(ratsdf_group* g, int n, const void* cons
     HIPCHK(hipEventRecord(g->ev_member[(size_t)s], g->eng[(size_t)s]->stream));
     HIPCHK(hipStreamWaitEvent(g->stream, g->ev_member[(size_t)s], 0));
   }
-  HIPCHK(hipMemcpyAsync(d_engs, g->h_engs[slot].as<EngineDev>(), (size_t)S * sizeof(EngineDev),
-                        hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipMemcpyAsync(d_jobs, hj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipEventRecord(g->ev_stage[slot], g->stream));
+  STCHK(g->tables.copy(d_engs, 0, (size_t)S * sizeof(EngineDev), g->stream));
+  STCHK(g->tables.commit(d_jobs, jobs_off, job_bytes, g->stream));
 
   // ---- launches ----
   const bool fused = e0->fused_serial && e0->vpl != 1;

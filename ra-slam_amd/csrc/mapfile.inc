@@ -151,17 +151,17 @@ struct MapStaging {
   uint8_t* host[2] = {nullptr, nullptr};  // (views of the above)
   uint8_t* dev[2] = {nullptr, nullptr};
   int32_t* d_idx = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  HipEvent ev[2];  // (declared behind the memory: they go first)
   ~MapStaging() {  // (the copies the events stand for have finished before the members free their memory)
-    for (int i = 0; i < 2; ++i)
-      if (ev[i]) (void)hipEventSynchronize(ev[i]), (void)hipEventDestroy(ev[i]);
+    for (HipEvent& x : ev)
+      if (x) (void)hipEventSynchronize(x);
   }
   int init(const std::vector<int32_t>& idx, hipStream_t s) {
     const size_t bytes = (size_t)kMapChunk * kMapRecordBytes;
     for (int i = 0; i < 2; ++i) {
       STCHK(host_mem[i].alloc(bytes));
       STCHK(dev_mem[i].alloc(bytes));
-      HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+      STCHK(ev[i].create(hipEventDisableTiming));
       host[i] = host_mem[i].as<uint8_t>();
       dev[i] = dev_mem[i].as<uint8_t>();
     }
@@ -521,8 +521,7 @@ int ratsdf_load_map(ratsdf_engine* e, const char* path) {
   FileCloser fc{f};
   // the file is good: everything the engine has enqueued finishes, then the map is replaced
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (e->copy_stream) HIPCHK(hipStreamSynchronize(e->copy_stream));
-  if (e->copy_stream2) HIPCHK(hipStreamSynchronize(e->copy_stream2));
+  STCHK(e->ring.drain());
   const MapHeader& h = m.h;
   Table& t = e->tab;
   int st = RATSDF_OK;

@@ -41,7 +41,7 @@ static int download_selected(ratsdf_engine* e, bool semantic, void** out, size_t
     // the caller owns `host` (ratsdf_free_buffer).  A large result is copied out by the engine's helper threads side
     // by side: the destination is fresh memory, and first-touch page faults (10 k of them for the 41 MB of a
     // GatherValid on the bench map) are what the single-threaded copy spent most of its time on
-    HostCopyPool* cp = bytes >= ((size_t)4 << 20) ? e->host_copy_pool() : nullptr;
+    HostCopyPool* cp = bytes >= ((size_t)4 << 20) ? e->ring.copy_pool() : nullptr;
     if (cp) {
       HostCopyPool::Piece pieces[16];
       int np = 0;

@@ -35,6 +35,8 @@
 #include "kernels_resample.h"
 #include "kernels_coarsen.h"
 #include "hip_mem.h"
+#include "hip_handles.h"
+#include "stage_plan.h"
 #include "workspace.h"
 #include "cand_shares.h"
 #include "../../include/ratsdf_sample.h"
@@ -145,8 +147,6 @@ __global__ void k_init_heap(int32_t* heap, int32_t n) {   // heap_init_kernel, v
 constexpr uint32_t kSlowCap = kSlowSortCap;
 constexpr int kDefaultVPL = 2;  // voxels per lane in k_integrate (RATSDF_VPL=2|4|8 overrides: tuning)
 constexpr uint32_t kSlowDelCap = 1u << 16;
-constexpr int kStageSlots = 16;  // frames of the host-image entry points in flight (uploads run ahead)
-constexpr int kUploadRun = 4;    // frames that go up with one copy when they lie side by side in page-locked memory
 
 }  // namespace
 
@@ -166,84 +166,7 @@ struct StreamDrain {
   ~StreamDrain() { (void)hipStreamSynchronize(stream); }
 };
 
-// Staging copies of the host-image entry points (caller's pageable images -> the engine's page-locked slot):
-// a 640x480 frame is 4.6 MB, which one core copies at ~10 GB/s -- 2 200 frames/s before anything else
-// happens.  The images of a frame are copied side by side by a few helper threads (started on first use,
-// parked on a condition variable in between); the caller takes the last piece itself.
-class HostCopyPool {
- public:
-  struct Piece {
-    void* dst;
-    const void* src;
-    size_t bytes;
-  };
-  // (thread creation can fail -- RLIMIT_NPROC, a cgroup's pids limit -- and nothing may be thrown through the C
-  // ABI: the pool carries on with the helpers that did start; with none, copy() is a plain memcpy loop)
-  explicit HostCopyPool(unsigned helpers) {
-    for (unsigned i = 0; i < helpers; ++i) {
-      try {
-        threads_.emplace_back([this] { run(); });
-      } catch (...) {
-        break;
-      }
-    }
-  }
-  ~HostCopyPool() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : threads_) t.join();
-  }
-  // copies every piece; returns when all are done (one caller at a time: the engine's entry points are
-  // serialised per handle, SURVEY 8b "Threading")
-  void copy(const Piece* pieces, int n) {
-    if (n <= 0) return;
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      pieces_ = pieces;
-      next_ = 0;
-      count_ = n - 1;  // the caller keeps the last one
-      pending_.store(n - 1, std::memory_order_relaxed);
-    }
-    if (n > 1) cv_.notify_all();
-    memcpy(pieces[n - 1].dst, pieces[n - 1].src, pieces[n - 1].bytes);
-    take_pieces();  // whatever the helpers have not picked up yet
-    while (pending_.load(std::memory_order_acquire) != 0) std::this_thread::yield();
-  }
-
- private:
-  void take_pieces() {
-    for (;;) {
-      const Piece* p = nullptr;
-      {
-        std::lock_guard<std::mutex> lk(m_);
-        if (next_ < count_) p = &pieces_[next_++];
-      }
-      if (!p) return;
-      memcpy(p->dst, p->src, p->bytes);
-      pending_.fetch_sub(1, std::memory_order_release);
-    }
-  }
-  void run() {
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [this] { return stop_ || next_ < count_; });
-        if (stop_) return;
-      }
-      take_pieces();
-    }
-  }
-  std::vector<std::thread> threads_;
-  std::mutex m_;
-  std::condition_variable cv_;
-  const Piece* pieces_ = nullptr;
-  int next_ = 0, count_ = 0;
-  std::atomic<int> pending_{0};
-  bool stop_ = false;
-};
+#include "stage_ring.inc"
 
 // The workspace of a box read-out: grown and carved by ratsdf_engine::workspace, with a layout of workspace.h.
 struct Workspace {
@@ -251,8 +174,8 @@ struct Workspace {
   size_t cap = 0;  // items (voxels, cells of the block grid) it was laid out for
 };
 
-// What the engine owns of device and page-locked host memory: every buffer has ONE owner (hip_mem.h), and free_all()
-// drops them all by assigning an empty EngineMem.  `fixed` owns what is allocated once, at creation, pix_mem / rank_mem
+// What the engine owns of device and page-locked host memory: every buffer has ONE owner (hip_mem.h), and
+// ~ratsdf_engine drops them all by assigning an empty EngineMem.  `fixed` owns what is allocated once, at creation, pix_mem / rank_mem
 // the image-sized buffers (ensure_image): the typed pointers in Table, Pool and the engine's fields are views of them
 // (those structures go to the kernels by value).  A buffer that grows on demand is its own owner; a capacity counted
 // in other units than bytes (pixels, voxels, a Workspace's items) is zero while its buffers are replaced, so a failed
@@ -275,8 +198,6 @@ struct EngineMem {
   DevMem d_fuse;       // map fusion (fuse.inc): positions | source pool indices | done bits | counters of one chunk
   DevMem d_occ;        // ray casting: hashed occupancy of the blocks (kernels_raycast.h), built per rendering
   DevMem d_mc;         // marching-cubes tables, built on first use
-  HostMem h_stage;     // staging ring of the host-image entry points (ratsdf_engine::stage_pix)
-  DevMem d_stage;
 
   template <class T>
   static int own(std::vector<DevMem>& set, T** view, size_t bytes) {
@@ -288,11 +209,11 @@ struct EngineMem {
 };
 
 // Timing of the dominant kernel (k_integrate / k_integrate_g) with HIP events attached to the dispatch itself; an
-// engine and a group each hold one.
+// engine and a group each hold one (declared behind the stream it times: its events go before the stream does).
 struct KernelTimer {
   bool on = false;
   int mode = 1;  // 1: every 4th frame, sums only; 2 (engines): every frame, per-frame records
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+  std::vector<std::pair<HipEvent, HipEvent>> prof_events;
   size_t used = 0;
   uint64_t frame = 0;
   double ms = 0;
@@ -302,13 +223,10 @@ struct KernelTimer {
   // pairs for the next `k` timed frames exist afterwards (what may fail, apart from the launches)
   int reserve(size_t k) {
     while (prof_events.size() < used + k) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        return RATSDF_ERR_DEVICE;
-      }
-      prof_events.emplace_back(a, b);
+      HipEvent a, b;
+      STCHK(a.create(hipEventDefault));
+      STCHK(b.create(hipEventDefault));
+      prof_events.emplace_back(std::move(a), std::move(b));
     }
     return RATSDF_OK;
   }
@@ -316,7 +234,8 @@ struct KernelTimer {
   // otherwise (sampled: events perturb the stream; mode 2 times every frame, for latency distributions)
   std::pair<hipEvent_t, hipEvent_t> take() {
     if (!on || (mode != 2 && frame++ % 4 != 0) || used == prof_events.size()) return {nullptr, nullptr};
-    return prof_events[used++];
+    const auto& ev = prof_events[used++];
+    return {ev.first, ev.second};
   }
   bool full() const { return on && used >= (mode == 2 ? 60000u : 4096u); }
   // `final`: nothing follows the timed frames (a read-out).  An intermediate drain in mode 2 (the event pool is
@@ -352,18 +271,15 @@ struct KernelTimer {
     n = 0;
     return st;
   }
-  void destroy() {
-    for (auto& ev : prof_events) {
-      (void)hipEventDestroy(ev.first);
-      (void)hipEventDestroy(ev.second);
-    }
-    prof_events.clear();
-  }
 };
 
 struct ratsdf_engine : EngineMem {
   int device = 0;
-  hipStream_t stream = nullptr;
+  // The handles (hip_handles.h) leave in the reverse of their declaration: `ring`, then `timer`'s events, then
+  // `stream` -- behind the drain, the graphs and the memory, which are ~ratsdf_engine's.
+  HipStream stream;
+  KernelTimer timer;         // profiling of the dominant kernel
+  StageRing ring;            // staging of the host-image entry points (stage_ring.inc)
   float vs = 0, trunc = 0;
   int block_bits = 0, bucket_bits = 0;
   int shard_rank = 0, shard_count = 1, shard_slab_bits = 2;
@@ -466,55 +382,36 @@ struct ratsdf_engine : EngineMem {
   SlowDelete* slowdel[2] = {nullptr, nullptr};
 
 
-  // staging for the host-image entry points: kStageSlots frames of 16 bytes/pixel each
-  size_t stage_pix = 0;
-  hipEvent_t stage_ev[kStageSlots] = {};  // upload of the slot's last user has been executed
-  hipEvent_t use_ev[kStageSlots + 1] = {};  // the frame that read the slot has been executed (+1: call fence)
-  hipStream_t copy_stream = nullptr;   // uploads of ratsdf_integrate_batch: even frames
-  hipStream_t copy_stream2 = nullptr;  // ... odd frames (two copy engines: one sustains ~31 GB/s)
-  // Both host-image entry points use the slots as ONE ring (slot = stage_no % kStageSlots, counted over every
-  // frame either of them has taken) and neither waits for its frames: what a slot's next user has to wait for is
-  // in the slot's two events, whichever call recorded them -- no fence between calls.
-  uint64_t stage_no = 0;
   // a frame with ht / lt has been integrated, or blocks were imported with their probabilities (FrameParams::segm_live)
   mutable bool ever_sem = false;
   bool sync_integrate = false;         // RATSDF_SYNC_INTEGRATE=1: wait for every frame (the round-3 behaviour)
-  HostCopyPool* copy_pool = nullptr;   // started on first use: host_copy_pool()
-  HostCopyPool* host_copy_pool() {     // (nullptr when it cannot be had: the callers copy by themselves then)
-    if (!copy_pool) copy_pool = new (std::nothrow) HostCopyPool(3);
-    return copy_pool;
-  }
 
   // HIP graphs of the batch entry point (ratsdf_integrate_device_batch): the launches of an n-frame batch are
   // captured once per (image size, n) -- the kernels of the group path with one member, which take every
   // per-frame operand (pose, intrinsics, image pointers, counter-set parity) from a FrameJob table in device
   // memory -- and replayed with a fresh table.  Host cost per frame: a table row instead of two launches.
+  // (destruction, the reverse of the declarations: the executable and the graph, then the tables' events and memory;
+  // the engine's stream has been drained before a BatchGraph goes)
   struct BatchGraph {
     int H = 0, W = 0, n = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    DevMem d_jobs;      // FrameJob[n]
-    HostMem h_jobs[2];  // page-locked, used alternately
-    hipEvent_t ev[2] = {nullptr, nullptr};     // the copy out of h_jobs[i] has been executed
-    unsigned turn = 0;
     uint64_t last_use = 0;
+    DevMem d_jobs;   // FrameJob[n]
+    TwinTable jobs;  // ... and its page-locked sides
+    HipGraph graph;
   };
   std::vector<BatchGraph> graphs;
   bool use_graphs = true;                // RATSDF_GRAPH=0: every frame launched by itself
   uint64_t graph_clock = 0;
-  void free_graph(BatchGraph& g);
   int batch_graph(int n, int H, int W, BatchGraph** out);
   struct GraphShape {
     int H, W, n;
   };
   std::vector<GraphShape> graph_failed;  // shapes whose capture failed once: launched frame by frame from then on
 
-  KernelTimer timer;         // profiling of the dominant kernel
   uint64_t prof_batch = 0;   // (mode 1: every fourth batch carries the events, ratsdf_integrate_device_batch)
 
-  int free_all();
+  ~ratsdf_engine();
   int ensure_image(size_t npix, size_t nranks);
-  int ensure_stage(size_t npix);
   EngineDev record() const;
   int upload_record();
   RankBufs rank_bufs(uint32_t nranks) const;
@@ -554,19 +451,12 @@ struct ratsdf_engine : EngineMem {
   Geom geometry(int H, int W, bool has_next, int split_a, int split_b, bool b_launched) const;
   int lookahead_split(size_t npix) const;
   bool graph_eligible(int n, int H, int W) const;
-  // A slot of the staging ring (depth | ht | lt | rgb, 16 bytes per pixel of the ring's largest image): its
-  // page-locked and its device memory, for an image of npix pixels.
-  struct StageSlot {
-    uint8_t *h, *d;
-    size_t npix;
-    FrameIn input(const ratsdf_intrinsics* K, const ratsdf_pose* T, bool sem) const {
-      return FrameIn{d + npix * 12, d, sem ? d + npix * 4 : nullptr, sem ? d + npix * 8 : nullptr, K, T};
-    }
-  };
-  StageSlot stage_slot(int slot, size_t npix) const;
-  void stage_fill(const StageSlot& s, const void* rgb, const void* depth, const void* ht, const void* lt, int parts);
-  int stage_upload(const StageSlot& s, bool sem, hipStream_t cs);
-  int stage_fail(int status);
+  // the frame in slot i of the staging ring, as the frame path takes it
+  FrameIn ring_input(int i, size_t npix, const ratsdf_intrinsics* K, const ratsdf_pose* T, bool sem) const {
+    const uint8_t* d = ring.slot(i, npix).d;
+    return FrameIn{d + npix * 12, d, sem ? d + npix * 4 : nullptr, sem ? d + npix * 8 : nullptr, K, T};
+  }
+  int host_image_fail(int status);
 };
 
 FrameParams ratsdf_engine::base_params() const {
@@ -592,26 +482,14 @@ FrameParams ratsdf_engine::base_params() const {
   return P;
 }
 
-int ratsdf_engine::free_all() {
+// What is not ownership: the streams are drained, and the order -- the graphs, then the memory (the base class would
+// go last), then the members' handles: the ring's, the timer's, the stream (see their declarations).
+ratsdf_engine::~ratsdf_engine() {
   if (stream) (void)hipStreamSynchronize(stream);
-  if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-  if (copy_stream2) (void)hipStreamSynchronize(copy_stream2);
+  (void)ring.drain();
   if (stream) (void)hipStreamSynchronize(stream);
-  delete copy_pool;
-  copy_pool = nullptr;
-  for (auto& g : graphs) free_graph(g);
   graphs.clear();
-  // memory: the views in tab / pool and the engine's raw pointers dangle from here on (the engine is deleted next)
   static_cast<EngineMem&>(*this) = EngineMem();
-  for (auto& ev : stage_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : use_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (copy_stream) (void)hipStreamDestroy(copy_stream);
-  if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
-  timer.destroy();
-  if (stream) (void)hipStreamDestroy(stream);
-  return RATSDF_OK;
 }
 
 RankBufs ratsdf_engine::rank_bufs(uint32_t nranks) const {
@@ -711,75 +589,10 @@ int ratsdf_engine::ensure_image(size_t npix, size_t nranks) {
   return upload_record();
 }
 
-int ratsdf_engine::ensure_stage(size_t npix) {
-  if (npix <= stage_pix) return RATSDF_OK;
-  if (copy_stream) HIPCHK(hipStreamSynchronize(copy_stream));
-  if (copy_stream2) HIPCHK(hipStreamSynchronize(copy_stream2));
-  HIPCHK(hipStreamSynchronize(stream));
-  stage_pix = 0;  // (a failure below leaves no capacity: the next call comes through here again)
-  const size_t bytes = npix * 16 * kStageSlots;  // per slot: depth 4 + ht 4 + lt 4 + rgb 3 (padded to 4)
-  h_stage.reset();
-  d_stage.reset();
-  STCHK(h_stage.alloc(bytes));
-  STCHK(d_stage.alloc(bytes));
-  for (int i = 0; i < kStageSlots; ++i)
-    if (!stage_ev[i]) HIPCHK(hipEventCreateWithFlags(&stage_ev[i], hipEventDisableTiming));
-  for (int i = 0; i <= kStageSlots; ++i)
-    if (!use_ev[i]) HIPCHK(hipEventCreateWithFlags(&use_ev[i], hipEventDisableTiming));
-  if (!copy_stream) HIPCHK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-  if (!copy_stream2) HIPCHK(hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking));
-  stage_pix = npix;
-  return RATSDF_OK;
-}
-
-// (the slot stride is the ring's, not the call's: a smaller image after a larger one must land in the SAME slot
-// memory the slot's events guard -- with a per-call stride its bytes would fall inside other slots that frames of
-// earlier calls, which are not waited for, may still be reading)
-ratsdf_engine::StageSlot ratsdf_engine::stage_slot(int slot, size_t npix) const {
-  const size_t off = (size_t)slot * stage_pix * 16;
-  return StageSlot{h_stage.as<uint8_t>() + off, d_stage.as<uint8_t>() + off, npix};
-}
-
-// The caller's pageable images into the slot's page-locked memory, side by side by the copy helpers (HostCopyPool);
-// every image in `parts` pieces of about equal size.  The slot's last upload must have left that memory.
-void ratsdf_engine::stage_fill(const StageSlot& s, const void* rgb, const void* depth, const void* ht, const void* lt,
-                               int parts) {
-  HostCopyPool::Piece pieces[8];
-  int np = 0;
-  auto add = [&](size_t off, const void* src, size_t bytes) {
-    const size_t step = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
-    for (size_t o = 0; o < bytes; o += step)
-      pieces[np++] = HostCopyPool::Piece{s.h + off + o, (const uint8_t*)src + o, std::min(step, bytes - o)};
-  };
-  add(0, depth, s.npix * 4);
-  if (ht) {
-    add(s.npix * 4, ht, s.npix * 4);
-    add(s.npix * 8, lt, s.npix * 4);
-  }
-  add(s.npix * 12, rgb, s.npix * 3);
-  if (HostCopyPool* cp = host_copy_pool()) {
-    cp->copy(pieces, np);
-  } else {
-    for (int i = 0; i < np; ++i) memcpy(pieces[i].dst, pieces[i].src, pieces[i].bytes);
-  }
-}
-
-// ... and from there into its device memory: one copy with semantics, depth and rgb without (no ht, lt)
-int ratsdf_engine::stage_upload(const StageSlot& s, bool sem, hipStream_t cs) {
-  if (sem) {
-    HIPCHK(hipMemcpyAsync(s.d, s.h, s.npix * 15, hipMemcpyHostToDevice, cs));
-  } else {
-    HIPCHK(hipMemcpyAsync(s.d, s.h, s.npix * 4, hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(s.d + s.npix * 12, s.h + s.npix * 12, s.npix * 3, hipMemcpyHostToDevice, cs));
-  }
-  return RATSDF_OK;
-}
-
 // A failed host-image call: whatever happened, nothing stays queued that reads a half-prepared slot or the caller's
 // buffers.
-int ratsdf_engine::stage_fail(int status) {
-  (void)hipStreamSynchronize(copy_stream);
-  (void)hipStreamSynchronize(copy_stream2);
+int ratsdf_engine::host_image_fail(int status) {
+  (void)ring.drain();
   abandon_pipeline();
   return status;
 }
@@ -1223,14 +1036,6 @@ static bool finite_frame(const ratsdf_intrinsics& K, const ratsdf_pose& T, float
   return true;
 }
 
-void ratsdf_engine::free_graph(BatchGraph& g) {
-  if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  if (g.graph) (void)hipGraphDestroy(g.graph);
-  for (int i = 0; i < 2; ++i)
-    if (g.ev[i]) (void)hipEventDestroy(g.ev[i]);
-  g = BatchGraph();  // (and with it the job tables)
-}
-
 // The launches of a batch whose operands lie in device tables: n frames of S members each (blockIdx.y), engine
 // records in `engs`, frame f of member s in d_jobs[f * S + s].  k_cand_g for the first frame (nobody looked ahead
 // for it: its candidate pass runs in line), then per frame k_front_g, k_alloc_rank_g when the serial role is a launch
@@ -1330,8 +1135,7 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
     size_t victim = 0;
     for (size_t i = 1; i < graphs.size(); ++i)
       if (graphs[i].last_use < graphs[victim].last_use) victim = i;
-    HIPCHK(hipStreamSynchronize(stream));
-    free_graph(graphs[victim]);
+    HIPCHK(hipStreamSynchronize(stream));  // (nothing queued replays the graph that goes)
     graphs.erase(graphs.begin() + (long)victim);
   }
   BatchGraph g;
@@ -1341,25 +1145,20 @@ int ratsdf_engine::batch_graph(int n, int H, int W, BatchGraph** out) {
   auto fail = [&](const char* what) {
     fprintf(stderr, "[ratsdf] batch graph %dx%d x %d: %s failed; batches of this shape are launched frame by frame\n",
             W, H, n, what);
-    free_graph(g);
     graph_failed.push_back(GraphShape{H, W, n});
     return RATSDF_ERR_DEVICE;
   };
   if (g.d_jobs.alloc((size_t)n * sizeof(FrameJob)) != RATSDF_OK) return fail("hipMalloc");
   FrameJob* const d_jobs = g.d_jobs.as<FrameJob>();
-  for (int i = 0; i < 2; ++i)
-    if (g.h_jobs[i].alloc((size_t)n * sizeof(FrameJob)) != RATSDF_OK ||
-        hipEventCreateWithFlags(&g.ev[i], hipEventDisableTiming) != hipSuccess)
-      return fail("staging allocation");
+  if (g.jobs.grow((size_t)n * sizeof(FrameJob)) != RATSDF_OK) return fail("staging allocation");
   // (graph_eligible: the serial role rides in k_integrate_g, whose first 8 extra workgroups are its own)
   const Geom g1 = geometry(H, W, true, lookahead_split((size_t)H * W), 0, false);
   const Geom g0 = geometry(H, W, false, 0, 0, false);
   if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) != hipSuccess) return fail("hipStreamBeginCapture");
   const Enqueued q = enqueue_jobs(stream, (EnginePtr)d_eng, d_jobs, n, 1, g0, g1, commit_rotation(g0.grid, g0.grid), 8u,
                                   (tab.tail_on ? 1u : 0u) | front_prio, vpl, nullptr);
-  if (hipStreamEndCapture(stream, &g.graph) != hipSuccess || q.status != RATSDF_OK || !g.graph)
-    return fail("capture");
-  if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) return fail("hipGraphInstantiate");
+  if (g.graph.end_capture(stream) != RATSDF_OK || q.status != RATSDF_OK) return fail("capture");
+  if (g.graph.instantiate() != RATSDF_OK) return fail("hipGraphInstantiate");
   g.last_use = ++graph_clock;
   graphs.push_back(std::move(g));
   *out = &graphs.back();
@@ -1469,13 +1268,13 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   e->shard_count = cfg->shard_count > 1 ? cfg->shard_count : 1;
   e->shard_slab_bits = cfg->shard_slab_bits > 0 ? cfg->shard_slab_bits : 2;
   e->S = (int)ceilf(2.f * e->trunc / e->vs / RATSDF_BLOCK_LEN) + 2;
-  // What the environment may change in the shipped library: the two documented behaviours below (and
-  // RATSDF_COPY_STREAMS in ratsdf_integrate_batch).  Every tuning and ablation switch of the measurements in
+  // What the environment may change in the shipped library: the three documented behaviours below.  Every tuning and ablation switch of the measurements in
   // DESIGN.md / profiles/ -- voxels per lane, look-ahead split, grid, the serial role as a launch of its own or at
   // the tail of k_front, fault injection -- exists in the diagnostic build only (make stamps, -DRATSDF_STAMPS),
   // together with the kernel variants it selects.
   if (const char* v = getenv("RATSDF_SYNC_INTEGRATE")) e->sync_integrate = atoi(v) != 0;
   if (const char* v = getenv("RATSDF_GRAPH")) e->use_graphs = atoi(v) != 0;
+  if (const char* v = getenv("RATSDF_COPY_STREAMS")) e->ring.two_streams = atoi(v) != 1;
 #ifdef RATSDF_STAMPS
   if (const char* v = getenv("RATSDF_VPL")) {
     const int x = atoi(v);
@@ -1537,13 +1336,12 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   do {                                   \
     if ((expr) != hipSuccess) {          \
       fprintf(stderr, "[ratsdf] create failed: %s\n", #expr); \
-      e->free_all();                     \
       delete e;                          \
       return RATSDF_ERR_DEVICE;          \
     }                                    \
   } while (0)
 
-  CREATE_CHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  CREATE_CHK(e->stream.create(hipStreamNonBlocking));
   CREATE_CHK(e->own(e->fixed, &t.entries, (size_t)t.num_entry * sizeof(Entry)));
   CREATE_CHK(e->own(e->fixed, &t.claim, (size_t)t.num_bucket * 4));
   // occupancy bitmap, and behind it the dirty bitmap of the directory delta (device_types.h: Table)
@@ -1624,7 +1422,6 @@ int ratsdf_create_ex(const ratsdf_config* cfg, ratsdf_engine** out) {
   CREATE_CHK(hipGetLastError());
   if (bt != 192u) {
     fprintf(stderr, "[ratsdf] create failed: the workgroup size is not where block_threads() reads it (code object ABI?)\n");
-    e->free_all();
     delete e;
     return RATSDF_ERR_DEVICE;
   }
@@ -1645,7 +1442,6 @@ int ratsdf_create(float voxel_size, float truncation, int device, ratsdf_engine*
 
 int ratsdf_destroy(ratsdf_engine* e) {
   ENTRY(e, true);
-  e->free_all();
   delete e;
   return RATSDF_OK;
 }
@@ -1676,14 +1472,12 @@ int ratsdf_integrate_device_batch(ratsdf_engine* e, int n, const void* const* d_
     STCHK(e->ensure_image(npix, npix * (size_t)e->S));
     ratsdf_engine::BatchGraph* g = nullptr;
     if (e->batch_graph(n, height, width, &g) == RATSDF_OK && g) {
-      const unsigned turn = g->turn++ & 1u;
-      HIPCHK(hipEventSynchronize(g->ev[turn]));  // the copy that last used this staging table is done
-      FrameJob* hj = g->h_jobs[turn].as<FrameJob>();
+      void* side = nullptr;
+      STCHK(g->jobs.acquire(&side));  // (the copy that last used this side of the table is done)
+      FrameJob* hj = static_cast<FrameJob*>(side);
       for (int i = 0; i < n; ++i) e->fill_job(hj[i], input(i), height, width, max_depth, e->parity + (unsigned)i);
-      if (hipMemcpyAsync(g->d_jobs.as<FrameJob>(), hj, (size_t)n * sizeof(FrameJob), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-          hipEventRecord(g->ev[turn], e->stream) != hipSuccess)
-        return RATSDF_ERR_DEVICE;
-      if (hipGraphLaunch(g->exec, e->stream) != hipSuccess) {
+      STCHK(g->jobs.commit(g->d_jobs.as<FrameJob>(), 0, (size_t)n * sizeof(FrameJob), e->stream));
+      if (hipGraphLaunch(g->graph.exec(), e->stream) != hipSuccess) {
         e->abandon_pipeline();
         return RATSDF_ERR_DEVICE;
       }
@@ -1733,29 +1527,26 @@ int ratsdf_integrate(ratsdf_engine* e, const uint8_t* rgb, const float* depth, c
   if (!finite_frame(*K, *T, max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   if (!ht || !lt) ht = lt = nullptr;  // modules/tsdf_module.cc:27-31
   const size_t npix = (size_t)height * width;
-  STCHK(e->ensure_stage(npix));
-  // The slots of the staging ring, one per call in turn (layout of a slot: depth | ht | lt | rgb).  The call
-  // returns when the caller's images sit in the slot's page-locked memory: the upload runs on a copy stream
-  // (it overlaps the previous frame's kernels), the frame's launches follow it on the engine's stream, and
-  // nothing here waits for the GPU unless the ring is full -- the slot's previous upload (8 calls ago) must
-  // have left its host memory before it is overwritten.  (Until round 4 every call ended with a stream
-  // synchronisation: 2 700 frames/s at 640x480, a third of it the single-threaded staging copy.)
-  const int slot = (int)(e->stage_no++ % kStageSlots);
-  const ratsdf_engine::StageSlot s = e->stage_slot(slot, npix);
-  HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // (an event never recorded counts as complete)
-  e->stage_fill(s, rgb, depth, ht, lt, ht ? 1 : 2);  // (a TSDF-only frame's two images in halves: four pieces either way)
-  hipStream_t cs = (slot & 1) ? e->copy_stream2 : e->copy_stream;
-  // the slot's device memory was last read by the frame that used it kStageSlots frames ago (of either host-image
-  // entry point): its use_ev.  Nothing else on the engine's stream reads the staging slots.
-  if (hipStreamWaitEvent(cs, e->use_ev[slot], 0) != hipSuccess) return e->stage_fail(RATSDF_ERR_DEVICE);
-  int st = e->stage_upload(s, ht != nullptr, cs);
-  if (st != RATSDF_OK) return e->stage_fail(st);
-  if (hipEventRecord(e->stage_ev[slot], cs) != hipSuccess ||
-      hipStreamWaitEvent(e->stream, e->stage_ev[slot], 0) != hipSuccess)
-    return e->stage_fail(RATSDF_ERR_DEVICE);
-  st = e->frame(s.input(K, T, ht != nullptr), nullptr, height, width, max_depth);
-  if (st != RATSDF_OK) return e->stage_fail(st);
-  if (hipEventRecord(e->use_ev[slot], e->stream) != hipSuccess) return e->stage_fail(RATSDF_ERR_DEVICE);
+  StageRing& ring = e->ring;
+  STCHK(ring.grow(npix, e->stream));
+  // The slots of the staging ring, one per call in turn.  The call returns when the caller's images sit in the
+  // slot's page-locked memory: the upload runs on a copy stream (it overlaps the previous frame's kernels), the
+  // frame's launches follow it on the engine's stream, and nothing here waits for the GPU unless the ring is full --
+  // the slot's previous upload (kStageSlots calls ago) must have left its host memory before it is overwritten.
+  // (Until round 4 every call ended with a stream synchronisation: 2 700 frames/s at 640x480, a third of it the
+  // single-threaded staging copy.)
+  const int slot = stage_slot_of(ring.no++, 0);
+  auto fail = [&](int status) { return e->host_image_fail(status); };
+  // (a TSDF-only frame's two images in halves: four pieces either way)
+  int st = ring.upload(slot, npix, StageImages{rgb, depth, ht, lt}, StageFrom::kPageable, ring.copy[slot & 1], 1,
+                       ht ? 1 : 2);
+  if (st != RATSDF_OK) return fail(st);
+  if (hipStreamWaitEvent(e->stream, ring.up_ev[slot], 0) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
+  st = e->frame(e->ring_input(slot, npix, K, T, ht != nullptr), nullptr, height, width, max_depth);
+  if (st != RATSDF_OK) return fail(st);
+  // the slot's device memory is next written kStageSlots frames on (of either host-image entry point), behind this
+  // event.  Nothing else on the engine's stream reads the staging slots.
+  if (hipEventRecord(ring.use_ev[slot], e->stream) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
   if (!e->sync_integrate) return RATSDF_OK;
   return e->sticky();  // cudaStreamSynchronize(stream_), voxel_tsdf.cu:450
 }
@@ -1769,111 +1560,59 @@ int ratsdf_integrate_batch(ratsdf_engine* e, int n, const uint8_t* const* rgb,
     if (!rgb[i] || !depth[i] || !finite_frame(K[i], T[i], max_depth)) return RATSDF_ERR_BAD_ARGUMENT;
   if (n == 0) return e->sticky();
   const size_t npix = (size_t)height * width;
-  int st = e->ensure_stage(npix);
-  if (st != RATSDF_OK) return st;
-  const size_t slot_bytes = e->stage_pix * 16;  // the ring's stride (see ratsdf_integrate)
-  const uint64_t base = e->stage_no;            // frame i of this call takes slot (base + i) % kStageSlots
-  e->stage_no += (uint64_t)n;
-  auto slot_of = [&](int i) { return (int)((base + (uint64_t)i) % kStageSlots); };
+  StageRing& ring = e->ring;
+  STCHK(ring.grow(npix, e->stream));
+  const uint64_t base = ring.no;  // frame i of this call takes slot stage_slot_of(base, i)
+  ring.no += (uint64_t)n;
   auto sem = [&](int i) { return ht && lt && ht[i] && lt[i]; };  // tsdf_module.cc:27-31
-  // Uploads run on their own stream, up to kStageSlots frames ahead of the frames that use them, so
-  // the PCIe copy of later frames overlaps the integration of earlier ones (one stream would
-  // serialise them).  Per device slot: up_ev = its upload has been executed, use_ev = the frame that
-  // read it has been executed.  Layout of a slot: depth | ht | lt | rgb.
-  static const bool two_streams = !(getenv("RATSDF_COPY_STREAMS") && atoi(getenv("RATSDF_COPY_STREAMS")) == 1);
+  auto bytes_of = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
   // a frame whose four images lie side by side in one page-locked block in the slot's own order (ratsdf::TSDFSystem's
   // queue keeps them so): one copy instead of four -- each costs ~10 us of launch overhead on the copy engine
   auto packed = [&](int i) {
-    const uint8_t* h0 = reinterpret_cast<const uint8_t*>(depth[i]);
-    return pinned && sem(i) && reinterpret_cast<const uint8_t*>(ht[i]) == h0 + npix * 4 &&
-           reinterpret_cast<const uint8_t*>(lt[i]) == h0 + npix * 8 &&
-           reinterpret_cast<const uint8_t*>(rgb[i]) == h0 + npix * 12;
+    const uint8_t* h0 = bytes_of(depth[i]);
+    return pinned && sem(i) && bytes_of(ht[i]) == h0 + npix * 4 && bytes_of(lt[i]) == h0 + npix * 8 &&
+           bytes_of(rgb[i]) == h0 + npix * 12;
   };
-  unsigned copy_no = 0;
-  // uploads frames [i, i + *took), *took <= max_run: more than one when the frames are packed blocks that lie side
-  // by side in host memory at the ring's own stride (the blocks of one arena of ratsdf::HostBlockPool) and their
-  // slots do not wrap -- then ONE copy fills the slots (16 bytes per pixel: the 15 the frame has + the slot's pad)
-  auto upload = [&](int i, int max_run, int* took) -> int {
-    const int slot = slot_of(i);
-    int run = 1;
-    if (packed(i) && npix == e->stage_pix)
-      while (run < max_run && i + run < n && slot + run < kStageSlots && packed(i + run) &&
-             reinterpret_cast<const uint8_t*>(depth[i + run]) == reinterpret_cast<const uint8_t*>(depth[i]) + (size_t)run * slot_bytes)
-        ++run;
-    *took = run;
-    hipStream_t cs = ((copy_no++ & 1) && two_streams) ? e->copy_stream2 : e->copy_stream;
-    const ratsdf_engine::StageSlot s = e->stage_slot(slot, npix);
-    uint8_t* const d = s.d;
-    // (the slot's last reader: a frame of this call or of an earlier one; an event never recorded counts as complete)
-    for (int j = 0; j < run; ++j) HIPCHK(hipStreamWaitEvent(cs, e->use_ev[slot + j], 0));
-    const uint8_t* h0 = reinterpret_cast<const uint8_t*>(depth[i]);
-    if (packed(i)) {
-      HIPCHK(hipMemcpyAsync(d, h0, (size_t)(run - 1) * slot_bytes + npix * 15, hipMemcpyHostToDevice, cs));
-    } else if (pinned) {  // straight from the caller's page-locked buffers
-      HIPCHK(hipMemcpyAsync(d, depth[i], npix * 4, hipMemcpyHostToDevice, cs));
-      if (sem(i)) {
-        HIPCHK(hipMemcpyAsync(d + npix * 4, ht[i], npix * 4, hipMemcpyHostToDevice, cs));
-        HIPCHK(hipMemcpyAsync(d + npix * 8, lt[i], npix * 4, hipMemcpyHostToDevice, cs));
-      }
-      HIPCHK(hipMemcpyAsync(d + npix * 12, rgb[i], npix * 3, hipMemcpyHostToDevice, cs));
-    } else {
-      HIPCHK(hipEventSynchronize(e->stage_ev[slot]));  // the slot's last upload has left its page-locked memory
-      e->stage_fill(s, rgb[i], depth[i], sem(i) ? ht[i] : nullptr, sem(i) ? lt[i] : nullptr, 1);
-      STCHK(e->stage_upload(s, sem(i), cs));
-    }
-    for (int j = 0; j < run; ++j) HIPCHK(hipEventRecord(e->stage_ev[slot + j], cs));
-    return RATSDF_OK;
+  // ... and frame i + k a block k ring strides behind it (the blocks of one arena of ratsdf::HostBlockPool)
+  auto adjacent = [&](int i, int k) {
+    return npix == ring.pix && bytes_of(depth[i + k]) == bytes_of(depth[i]) + (size_t)k * ring.stride();
   };
-  auto input = [&](int i) { return e->stage_slot(slot_of(i), npix).input(&K[i], &T[i], sem(i)); };
-  // whatever happens, the caller's buffers (and the staging slots) are no longer in use on return
-  auto fail = [&](int status) { return e->stage_fail(status); };
+  // Uploads run on their own streams, ahead of the frames that use them (stage_plan.h), so the PCIe copy of later
+  // frames overlaps the integration of earlier ones (one stream would serialise them).
   // (No fence against earlier calls: frames of earlier host-image calls that are still in flight are what the
   // slots' events stand for, and nothing else on the engine's stream touches the staging slots.  Until round 5
   // every call began by making both copy streams wait for ALL earlier work of the engine's stream and ended with
   // a synchronisation: the link idled ~0.4 ms per 32-frame call, 13 % of it -- tools/copy_gaps.py.)
-  // Uploads are enqueued up to `ahead` frames in front of the frame being launched: slot (u % kStageSlots) was last
-  // read by frame u - kStageSlots, whose use_ev must have been RECORDED (i.e. that frame launched) before a copy
-  // stream is told to wait for it.
-  const int ahead = kStageSlots - 1;
-  int uploaded = 0;
-  for (int i = 0; i < n; ++i) {
-    // frame i's launches host the look-ahead of frame i+1: both uploads precede them
-    while (uploaded < n && uploaded <= i + 1) {
-      int took = 0;
-      st = upload(uploaded, std::min(kUploadRun, i + ahead - uploaded + 1), &took);
-      if (st != RATSDF_OK) return fail(st);
-      uploaded += took;
-    }
-    if (hipStreamWaitEvent(e->stream, e->stage_ev[slot_of(i)], 0) != hipSuccess ||
-        (i + 1 < n && hipStreamWaitEvent(e->stream, e->stage_ev[slot_of(i + 1)], 0) != hipSuccess))
-      return fail(RATSDF_ERR_DEVICE);
+  unsigned copy_no = 0;
+  auto upload = [&](int i, int max_run) {
+    const int slot = stage_slot_of(base, i);
+    const int run = stage_run_length(i, n, slot, max_run, packed, adjacent);
+    const StageImages im{rgb[i], depth[i], sem(i) ? ht[i] : nullptr, sem(i) ? lt[i] : nullptr};
+    const StageFrom from = packed(i) ? StageFrom::kPacked : pinned ? StageFrom::kPinned : StageFrom::kPageable;
+    return StageTook{run, ring.upload(slot, npix, im, from, ring.copy[(copy_no++ & 1u) && ring.two_streams], run)};
+  };
+  auto input = [&](int i) { return e->ring_input(stage_slot_of(base, i), npix, &K[i], &T[i], sem(i)); };
+  auto launch = [&](int i) -> int {
+    if (hipStreamWaitEvent(e->stream, ring.up_ev[stage_slot_of(base, i)], 0) != hipSuccess ||
+        (i + 1 < n && hipStreamWaitEvent(e->stream, ring.up_ev[stage_slot_of(base, i + 1)], 0) != hipSuccess))
+      return RATSDF_ERR_DEVICE;
     const ratsdf_engine::FrameIn cur = input(i);
     ratsdf_engine::FrameIn nxt{};
     if (i + 1 < n) nxt = input(i + 1);
-    st = e->frame(cur, i + 1 < n ? &nxt : nullptr, height, width, max_depth);
-    if (st != RATSDF_OK) return fail(st);
+    STCHK(e->frame(cur, i + 1 < n ? &nxt : nullptr, height, width, max_depth));
     // frame i's images were last read by its candidate pass, which ran in frame i-1's launches or
     // before; recording after frame i is the simple, safe point
-    if (hipEventRecord(e->use_ev[slot_of(i)], e->stream) != hipSuccess) return fail(RATSDF_ERR_DEVICE);
-    // run further ahead with the uploads while the queue is busy -- in whole runs (or the batch's tail), so that
-    // side-by-side frames keep going up together instead of one by one as slots fall free
-    while (uploaded < n) {
-      const int want = std::min(kUploadRun, n - uploaded);
-      if (uploaded + want - 1 > i + ahead) break;
-      int took = 0;
-      st = upload(uploaded, want, &took);
-      if (st != RATSDF_OK) return fail(st);
-      uploaded += took;
-    }
-  }
+    return hipEventRecord(ring.use_ev[stage_slot_of(base, i)], e->stream) == hipSuccess ? RATSDF_OK : RATSDF_ERR_DEVICE;
+  };
+  // whatever happens, the caller's buffers (and the staging slots) are no longer in use on return
+  auto fail = [&](int status) { return e->host_image_fail(status); };
+  int st = stage_schedule(n, upload, launch);
+  if (st != RATSDF_OK) return fail(st);
   // The call returns when the caller's buffers are no longer in use: at once for pageable images (they were copied
   // into the staging ring), after the last upload for page-locked ones.  It does not wait for the frames'
   // kernels -- the next call's uploads overlap them -- so a device error of these frames is reported by the next
   // entry point that synchronises, as for ratsdf_integrate.
-  if (pinned) {
-    if (hipStreamSynchronize(e->copy_stream) != hipSuccess || hipStreamSynchronize(e->copy_stream2) != hipSuccess)
-      return fail(RATSDF_ERR_DEVICE);
-  }
+  if (pinned && ring.drain() != RATSDF_OK) return fail(RATSDF_ERR_DEVICE);
   if (!e->sync_integrate) return RATSDF_OK;
   st = e->sticky();
   if (st == RATSDF_ERR_DEVICE) return fail(st);
@@ -1916,8 +1655,7 @@ int ratsdf_synchronize(ratsdf_engine* e) {
 // written them); otherwise they are rebuilt from the directory, ascending.
 static int rebuild_derived(ratsdf_engine* e, bool keep_heap) {
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (e->copy_stream) HIPCHK(hipStreamSynchronize(e->copy_stream));
-  if (e->copy_stream2) HIPCHK(hipStreamSynchronize(e->copy_stream2));
+  STCHK(e->ring.drain());
   Table& t = e->tab;
   const uint32_t occ_words = (t.num_entry + 63) / 64;
   const size_t nb = (size_t)t.num_block;
