@@ -22,6 +22,8 @@ constexpr uint32_t kMapRecordWords = 3 * 512;                 // {tsdf[512] | rg
 constexpr size_t kMapRecordBytes = (size_t)kMapRecordWords * 4;
 constexpr size_t kMapRgbBytes = 512 * 4;                      // rgbw[512] of a free block that has been in use
 constexpr uint32_t kMapChunk = 2048;                          // records per staging buffer (12 MiB)
+// k_map_pack / k_map_unpack take two records per workgroup in grids of at most 2048: a chunk never makes one stride
+static_assert((kMapChunk + 1) / 2 <= 2048u, "the pack and unpack grids cover a chunk in one sweep");
 
 struct MapHeader {  // 64 bytes, little-endian (the engine's hosts are)
   char magic[8];

@@ -21,6 +21,11 @@ struct ratsdf_labelset {
 constexpr size_t kLabelMaxPoints = (size_t)1 << 26;
 constexpr double kLabelMaxCells = (double)(1 << 24);
 constexpr unsigned kScoreGrid = 2048;  // workgroups of k_score_labels: they stride over the blocks
+// the most workgroups (of 256 threads) of the set builders' passes: beyond them a workgroup strides over the items
+constexpr unsigned kBoundsGrid = 1024;     // k_label_bounds over the points, k_mesh_bounds over max(vertices, triangles)
+constexpr unsigned kLabelFillGrid = 4096;  // k_label_count and k_label_scatter over the points
+constexpr unsigned kMeshRefsGrid = 4096;   // k_mesh_refs over the triangles (score_mesh.inc)
+constexpr unsigned kMeshCellsGrid = 8192;  // k_mesh_cells over the triangles, kMeshLanes lanes each (score_mesh.inc)
 
 // ---- what the builds of a label set and of a mesh set (score_mesh.inc) share ----
 
@@ -84,7 +89,7 @@ static int labelset_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* d
     STCHK(d_bounds.alloc(sizeof(hb)));
     HIPCHK(hipMemsetAsync(d_bounds.as<void>(), 0xFF, 12, e->stream));
     HIPCHK(hipMemsetAsync(d_bounds.as<uint8_t>() + 12, 0, sizeof(hb) - 12, e->stream));
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, kBoundsGrid);
     hipLaunchKernelGGL(k_label_bounds, dim3(grid), dim3(256), 0, e->stream, d_xyz, d_labels, n,
                        d_bounds.as<uint32_t>());
     HIPCHK(hipGetLastError());
@@ -115,7 +120,7 @@ static int labelset_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* d
     g.rec = s->rec.as<const float4>();
     g.start = s->start.as<const uint32_t>();
     g.label = s->label.as<const uint8_t>();
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, kLabelFillGrid);
     uint32_t* const cnt = d_cnt.as<uint32_t>();
     HIPCHK(hipMemsetAsync(cnt, 0, 4 * (ncell + 1), e->stream));
     hipLaunchKernelGGL(k_label_count, dim3(grid), dim3(256), 0, e->stream, d_xyz, n, g, cnt);

@@ -41,7 +41,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
     STCHK(d_bounds.alloc(sizeof(hb)));
     HIPCHK(hipMemsetAsync(d_bounds.as<void>(), 0xFF, 12, e->stream));
     HIPCHK(hipMemsetAsync(d_bounds.as<uint8_t>() + 12, 0, sizeof(hb) - 12, e->stream));
-    const unsigned grid = (unsigned)std::min<size_t>((std::max(nv, nt) + 255) / 256, 1024);
+    const unsigned grid = (unsigned)std::min<size_t>((std::max(nv, nt) + 255) / 256, kBoundsGrid);
     hipLaunchKernelGGL(k_mesh_bounds, dim3(grid), dim3(256), 0, e->stream, d_xyz, d_labels, nv, d_tri, nt,
                        d_bounds.as<uint32_t>());
     HIPCHK(hipGetLastError());
@@ -51,7 +51,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   const size_t kept = hb.kept;
-  const unsigned tgrid = (unsigned)std::min<size_t>((nt + 255) / 256, 4096);
+  const unsigned tgrid = (unsigned)std::min<size_t>((nt + 255) / 256, kMeshRefsGrid);
   MeshGrid& g = s->grid;
   double lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0}, cells[3] = {1, 1, 1};
   unsigned long long refs = 0;
@@ -84,7 +84,7 @@ static int labelmesh_build(ratsdf_engine* e, const float* d_xyz, const uint8_t* 
     g.rec = s->rec.as<const float4>();
     g.ref = s->ref.as<const uint32_t>();
     g.label = s->label.as<const uint8_t>();
-    const unsigned grid = (unsigned)std::min<size_t>((nt * kMeshLanes + 255) / 256, 8192);
+    const unsigned grid = (unsigned)std::min<size_t>((nt * kMeshLanes + 255) / 256, kMeshCellsGrid);
     uint32_t* const cnt = d_cnt.as<uint32_t>();
     HIPCHK(hipMemsetAsync(cnt, 0, 4 * (ncell + 1), e->stream));
     hipLaunchKernelGGL(k_mesh_cells<false>, dim3(grid), dim3(256), 0, e->stream, d_xyz, d_labels, nv, d_tri, nt, g,

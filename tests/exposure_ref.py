@@ -179,6 +179,48 @@ def exposure(state, origin, vs, points, lamps, max_range=np.inf, min_irradiance=
     return acc, mask, table, summary
 
 
+def exposure_pairs(state, origin, vs, points, lamps, max_range=np.inf, min_irradiance=0.0, unknown_occupied=False,
+                   dose=None):
+    """the contract per (point, lamp) pair, for callers that weight rows by a multiplicity (tests/capped_grid_cases.py
+    evaluates the unique rows of a long list): (dose [n], mask [n], visible [n, lamps] bool, lit [n, lamps] bool,
+    outside [n] bool, accepted [lamps] bool).  exposure()'s table and summary are sums over these: lit and
+    lit & (prob >= p_cutoff) per lamp, visible over all pairs, the rows with a mask, the outside rows, the accepted
+    lamps.  `dose` as in exposure()."""
+    vs = F(vs)
+    Z, Y, X = state.shape
+    dims = (X, Y, Z)
+    pts = np.asarray(points).reshape(-1)
+    lmp = np.asarray(lamps).reshape(-1)
+    npts, nl = len(pts), len(lmp)
+    assert nl <= MAX_LAMPS
+    blocking = blocking_of(state, unknown_occupied)
+    ppos, nrm = pts["pos"].astype(F).reshape(-1, 3), pts["normal"].astype(F).reshape(-1, 3)
+    lpos, power = lmp["pos"].astype(F).reshape(-1, 3), lmp["power"].astype(F)
+    with np.errstate(all="ignore"):
+        Lv, l_in = voxel_of(lpos / vs + F(0.5), origin, dims)
+        accepted = l_in & ~blocking[Lv[:, 2], Lv[:, 1], Lv[:, 0]]
+        sv, p_in = voxel_of((ppos / vs + nrm) + F(0.5), origin, dims)
+        outside = ~p_in
+        d = lpos[None, :, :] - ppos[:, None, :]
+        r2 = _dot3(d, d, None)
+        c = _dot3(np.broadcast_to(nrm[:, None, :], d.shape), d, None)
+        mr = F(max_range)
+        e = power[None, :] * (c / (r2 * np.sqrt(r2))) * INV_4PI
+    cand = (c > F(0)) & ~(r2 > mr * mr) & accepted[None, :] & ~outside[:, None]
+    pi, ki = np.nonzero(cand)
+    visible = np.zeros((npts, nl), dtype=bool)
+    if len(pi):
+        visible[pi, ki] = clear_walks(blocking, sv[pi], Lv[ki])
+    acc = np.zeros(npts, dtype=F) if dose is None else np.array(dose, dtype=F).reshape(-1).copy()
+    mask = np.zeros(npts, dtype=np.uint64)
+    with np.errstate(all="ignore"):
+        for k in range(nl):
+            acc = np.where(visible[:, k], acc + e[:, k], acc)
+            mask |= visible[:, k].astype(np.uint64) << np.uint64(k)
+        lit = visible & (e >= F(min_irradiance))
+    return acc, mask, visible, lit, outside, accepted
+
+
 def make_points(pos, normal, prob=0.5):
     pos = np.asarray(pos, dtype=F).reshape(-1, 3)
     p = np.zeros(len(pos), dtype=POINT_DTYPE)
